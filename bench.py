@@ -13,7 +13,17 @@ a = 2*pi, dt from One_code.mlx:111-112).  Rank 0 runs u0 = sin(2 pi x) (the gold
 rank j > 0 runs IC j of the synthetic ensemble.  N GPUs = an ensemble of N
 trajectories, one per GPU (weak scaling; the only exchange is the indicator sum).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--nsteps S] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--nsteps S]
+                                         the plain run: set up, warm up, time K steps, print
+                                         the result line (nothing else runs on the GPU or CPU)
+  python bench.py --full [--no-cpu-baseline] [--no-margin]
+                                         also what takes runs of its own after the timed steps:
+                                         the CPU baselines (the oracle and its C port), the
+                                         stream-copy bandwidth probe and the refine-decision
+                                         margin check (their fields are null in a plain line)
+  python bench.py --dump-outputs DIR     after the timed steps write what the last step computed
+                                         (the indicator |eta|, the adjoint state w^0, the refine
+                                         index and value) as DIR/<name>.npy, float64
   python bench.py --K 65536 --ics 1024   BASELINE config 4 (ensemble sharded over ranks,
                                          strong scaling)
   python bench.py --config 3             BASELINE config 3: Burgers-type flux + SlopeLimitN after
@@ -149,11 +159,23 @@ def parse(argv=None):
                       "adjoint (a refinement ranking, DESIGN.md 6c); p: the p-enriched DWR "
                       "error estimate (order-(N+1) adjoint x one-step residual of the prolonged "
                       "snapshots; implies --record snapshots)")
-  p.add_argument("--no-cpu-baseline", action="store_true")
+  p.add_argument("--full", action="store_true",
+                 help="after the timed steps also run what the headline figure does not need: "
+                      "the CPU baselines, the stream-copy bandwidth probe and the "
+                      "refine-decision margin check (off by default: a plain run sets up, warms "
+                      "up, times --steps steps and prints its line)")
+  p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                 help="after the timed steps write the arrays the last timed step computed "
+                      "(indicator, adjoint state, refine index and value) as DIR/<name>.npy in "
+                      "float64; above 60 MB in all, a fixed seeded sample of the larger arrays "
+                      "(config 3: warms up exactly --warmup steps, as --no-converge, since its "
+                      "mesh after the warm-up is the timed steps' input)")
+  p.add_argument("--no-cpu-baseline", action="store_true",
+                 help="with --full: skip the CPU baselines")
   p.add_argument("--no-margin", action="store_true",
-                 help="skip the refine-decision margin check after the timed region (it re-runs "
-                      "the sweep in another block shape: profiler passes use this so that every "
-                      "dispatch they average has the timed shape)")
+                 help="with --full: skip the refine-decision margin check after the timed region "
+                      "(it re-runs the sweep in another block shape: profiler passes use this so "
+                      "that every dispatch they average has the timed shape)")
   p.add_argument("--cpu-steps", type=int, default=12, help="time steps of the CPU sample")
   p.add_argument("--graph", action="store_true",
                  help="replay each sweep as a captured HIP graph (measured 1-3%% slower than "
@@ -167,6 +189,8 @@ def parse(argv=None):
     a.warmup = 4 if a.config == 3 else 10
   if a.indicator == "p":
     a.record = "snapshots"
+  if a.dump_outputs and a.config == 3:
+    a.no_converge = True  # the refined mesh the timed steps start from must not depend on timing
   return a
 
 
@@ -238,6 +262,42 @@ def stream_copy_gbs(dev, nbytes=1 << 30, reps=10):
     ts.append(e0.elapsed_time(e1) * 1e-3)
   del src, dst
   return 2.0 * nbytes / float(np.median(ts)) / 1e9
+
+
+DUMP_CAP_BYTES = 60 * 10**6  # --dump-outputs writes at most this much in all
+DUMP_SEED = 20260101
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+  """Write `arrays` (name -> 1-D float64 device tensor or host array) as path/<name>.npy
+  (<name>_rank<r>.npy with several ranks), float64.  Above DUMP_CAP_BYTES in all, every array
+  of more than 4096 entries is replaced by a sample of it at sorted indices drawn (with
+  replacement) from numpy's default_rng(DUMP_SEED), names taken in sorted order: the same
+  entries in every run with the same arguments.  Returns {name: [entries written, entries]}."""
+  import torch
+  os.makedirs(path, exist_ok=True)
+  small = 4096
+  total = sum(8 * int(np.prod(a.shape)) for a in arrays.values())
+  big = sum(8 * int(np.prod(a.shape)) for a in arrays.values() if int(np.prod(a.shape)) > small)
+  frac = 1.0 if total <= DUMP_CAP_BYTES else max(0.0, DUMP_CAP_BYTES - (total - big)) / big
+  rng = np.random.default_rng(DUMP_SEED)
+  written = {}
+  for name in sorted(arrays):
+    a = arrays[name]
+    n = int(np.prod(a.shape))
+    if frac < 1.0 and n > small:
+      idx = np.sort(rng.integers(0, n, size=int(n * frac)))
+      if isinstance(a, torch.Tensor):
+        a = a.reshape(-1).index_select(0, torch.as_tensor(idx, device=a.device))
+      else:
+        a = np.asarray(a).reshape(-1)[idx]
+    if isinstance(a, torch.Tensor):
+      a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+    written[name] = [int(a.size), n]
+  return written
 
 
 BASELINE_METRIC = "DOF-updates/sec, 1D DG advection fwd+adjoint sweep, N=4, K=1e6"
@@ -551,6 +611,17 @@ def main_config3(args, world, rank, dev):
   elapsed = max_over_ranks(time.perf_counter() - t0, world, dev, args.backend)
   total = sum_over_ranks(total, world, dev, args.backend)
   Np = N + 1
+  dumped = None
+  if args.dump_outputs:
+    # the last timed step's sweep ran on the mesh before its own split (one element fewer):
+    # its indicator, the adjoint state it left in snapshot N, and the refine indices so far
+    k_last = run.K - 1
+    n_last = Np * k_last
+    dumped = dump_outputs(args.dump_outputs, {
+        "eta": run._eta[:k_last],
+        "w": run._snaps[nsteps * n_last:(nsteps + 1) * n_last],
+        "refine_history": np.asarray(run.history, dtype=np.float64),
+    }, rank, world)
   k_mid = K + warm + args.steps // 2
   # forward steps per launch with snapshots (dg_burgers.hip chunk_nl): 2 only when tuned to 2;
   # the exchange: workgroup tiles (k_step_nl / k_adj_nl + k_adj_nl_wide) or overlapped waves
@@ -608,6 +679,7 @@ def main_config3(args, world, rank, dev):
       "refine_index": ref_idx,
       "refine_index_ranks": ranks_agree(ref_idx, world, dev, args.backend),
       "K_final": run.K,
+      "dumped_outputs": dumped,
   }
   # Counters from the committed config-3 profile (profiles/r03/collect_c3.sh: FETCH_SIZE /
   # WRITE_SIZE and SQ fp64 VALU passes of this bench), used when N and K match: HBM traffic
@@ -647,7 +719,7 @@ def main_config3(args, world, rank, dev):
           "source": src,
           "what": "fp64 flops issued per launch (PMC: 64 lanes x (2 FMA + ADD + MUL) wave "
                   "instructions, halo lanes included) / this run's launch time"}
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
     out["cpu_baseline"] = cpu_baseline_config3(N, K, 2)
   if rank == 0:
     print(json.dumps(out, allow_nan=False), flush=True)
@@ -890,6 +962,13 @@ def main(argv=None):
   if nonfinite:
     pkg.adaptive.check_indicator(float("nan"), ref_idx)  # raises FloatingPointError
   pkg.adaptive.check_indicator(ref_val, ref_idx)
+  dumped = None
+  if args.dump_outputs:
+    # what a caller of the timed path receives from its last step: the per-trajectory
+    # indicator magnitudes, the adjoint state w^0 (dJ/du^0) and the refine decision
+    dumped = dump_outputs(args.dump_outputs, {
+        "eta": sweep.eta, "w": sweep.w.reshape(-1),
+        "refine": np.array([ref_idx, ref_val], dtype=np.float64)}, rank, world)
 
   Np, ktot = N + 1, K * sweep.batch
   pmode = args.indicator == "p"
@@ -1030,7 +1109,7 @@ def main(argv=None):
   # DOF-updates, so its HBM roofline is 8 TB/s / that per-update average.
   single_step_bytes = (16.0 + 24.0 + 16.0 / Np) / 2.0
   single_step_roofline = HBM_PEAK_GBS * 1e9 / single_step_bytes * world
-  copy_gbs = stream_copy_gbs(dev) if rank == 0 else None
+  copy_gbs = stream_copy_gbs(dev) if rank == 0 and args.full else None
   import torch.distributed as dist
   dist_world = dist.get_world_size() if dist.is_initialized() else 1
   idx_ranks = ranks_agree(ref_idx, world, dev, args.backend)
@@ -1051,7 +1130,8 @@ def main(argv=None):
     f_fl, a_fl = fwd_fpu * Np * ktot * nsteps, adj_fpu * Np * ktot * nsteps
     adj_tf = (f_fl + a_fl) / (adj_launch_us * 1e-6) / 1e12
     halo_adj = (f_fl * halo_fwd + a_fl * halo_adj) / (f_fl + a_fl)
-  decision = refine_margin(sweep, one_step) if world == 1 and not args.no_margin else None
+  decision = (refine_margin(sweep, one_step)
+              if world == 1 and args.full and not args.no_margin else None)
   out = {
       "metric": metric_name(N, K),
       "value": value,
@@ -1133,6 +1213,7 @@ def main(argv=None):
       "host_issue_ms_per_step": host_issue / args.steps * 1e3,
       "library": {"path": os.path.relpath(pkg._lib.LIB_PATH, ROOT),
                   "override": bool(os.environ.get("DG_LIB_PATH"))},
+      "dumped_outputs": dumped,
   }
   if pmode:
     try:  # issued fp64 of k_adj_p from the SQ passes of the same bench (profiles/r04/p/)
@@ -1251,7 +1332,7 @@ def main(argv=None):
       raise RuntimeError("a dataflow work item gave up waiting for a producer")
   if len(set(idx_ranks)) != 1:
     raise RuntimeError(f"refine index differs across ranks: {idx_ranks}")
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
     cs = args.cpu_steps if not pmode else max(2, args.cpu_steps // 2)
     kw = dict(indicator=args.indicator, ics=min(2, n_total), ics_total=n_total)
     numpy_1t = cpu_baseline(N, K, cs, **kw)

@@ -112,3 +112,41 @@ def test_bench_p_indicator_accounting():
   for Np in range(2, 9):
     assert b.p_flops_per_update(Np) > b.eo_flops_per_update(Np + 1, True)
   assert b.halo_factor(1024, 50) == 1024 / 924.0
+
+
+def test_bench_full_and_dump_arguments():
+  """A plain run does only what its headline needs: --full (off by default) turns on the CPU
+  baselines, the stream-copy probe and the margin check; --dump-outputs names a directory, and
+  for config 3 (whose timed steps start from the mesh the warm-up refined) fixes the warm-up
+  to --warmup steps."""
+  b = _bench()
+  a = b.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+  assert not a.full and a.dump_outputs is None and not a.no_converge
+  a = b.parse(["--full", "--dump-outputs", "out"])
+  assert a.full and a.dump_outputs == "out" and not a.no_converge
+  assert b.parse(["--config", "3", "--dump-outputs", "out"]).no_converge
+
+
+def test_dump_outputs_writes_float64_and_samples_above_the_cap(tmp_path):
+  """dump_outputs: small sets are written whole as float64 .npy; above DUMP_CAP_BYTES in all
+  the large arrays become the same seeded sample in every call, small ones stay whole, and the
+  files together stay under the cap."""
+  import numpy as np
+  b = _bench()
+  eta = np.arange(1000, dtype=np.float64) * 0.5
+  ref = np.array([7.0, 0.25])
+  got = b.dump_outputs(str(tmp_path / "a"), {"eta": eta, "refine": ref})
+  assert got == {"eta": [1000, 1000], "refine": [2, 2]}
+  back = np.load(tmp_path / "a" / "eta.npy")
+  assert back.dtype == np.float64 and np.array_equal(back, eta)
+  assert np.array_equal(np.load(tmp_path / "a" / "refine.npy"), ref)
+  n = b.DUMP_CAP_BYTES // 8  # two arrays of the cap's size each: half of each is kept
+  w = np.arange(n, dtype=np.float64)
+  for d in ("b", "c"):
+    got = b.dump_outputs(str(tmp_path / d), {"w": w, "v": -w, "refine": ref}, rank=1, world=2)
+    assert got["refine"] == [2, 2] and got["w"][1] == n and 0 < got["w"][0] <= n // 2
+  files = sorted(os.listdir(tmp_path / "b"))
+  assert files == ["refine_rank1.npy", "v_rank1.npy", "w_rank1.npy"]
+  assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= b.DUMP_CAP_BYTES + 1024
+  wb, wc = np.load(tmp_path / "b" / "w_rank1.npy"), np.load(tmp_path / "c" / "w_rank1.npy")
+  assert np.array_equal(wb, wc) and np.all(np.diff(wb) >= 0) and wb[-1] < n

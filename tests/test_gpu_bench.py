@@ -30,7 +30,7 @@ def _run(args, timeout=240, env_extra=None):
 def test_bench_single_rank_line(gpu, dataflow):
   """The default line (the sweep as one dataflow launch, k_sweep_rp) and the launch-chain
   line (DG_REC_SWEEP=0: k_step_rp + k_adj_rp, timed per direction)."""
-  out = _run(["--K", "65536", "--steps", "3", "--warmup", "2", "--no-converge",
+  out = _run(["--full", "--K", "65536", "--steps", "3", "--warmup", "2", "--no-converge",
               "--no-cpu-baseline"], env_extra={"DG_REC_SWEEP": "1" if dataflow else "0"})
   assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup_effective"] == 2
   assert out["unit"] == "DOF-updates/s" and out["value"] > 0
@@ -70,7 +70,7 @@ def test_bench_p_estimate_line(gpu):
   prolonged one-step residual -- by default both as ONE dataflow launch (k_psweep, with the
   refine decision); its line carries the same roofline blocks and a CPU baseline of the
   oracle's p-estimate.  (The jump line run first carries the compiled oracle port's.)"""
-  out = _run(["--K", "65536", "--steps", "3", "--warmup", "2", "--no-converge",
+  out = _run(["--full", "--K", "65536", "--steps", "3", "--warmup", "2", "--no-converge",
               "--cpu-steps", "2"])
   assert out["indicator"] == "jump"
   # the jump line's CPU baseline: the oracle's C port on the host threads and on one, the
@@ -79,7 +79,7 @@ def test_bench_p_estimate_line(gpu):
   assert "C port" in cb["sample"] and cb["kind"] == "port" and cb["cores"] >= 1
   assert c1["cores"] == 1 and "C port" in c1["sample"] and "numpy" in cn["sample"]
   assert cb["value"] > 0 and c1["value"] > 0 and cn["value"] > 0
-  out = _run(["--K", "65536", "--steps", "3", "--warmup", "2", "--no-converge",
+  out = _run(["--full", "--K", "65536", "--steps", "3", "--warmup", "2", "--no-converge",
               "--indicator", "p", "--cpu-steps", "2"])
   assert out["indicator"] == "p" and out["config"]["record"] == "snapshots"
   assert out["roofline"]["kernel"].startswith("k_psweep<4+1")
@@ -104,3 +104,37 @@ def test_bench_self_launches_two_ranks(gpu, extra):
   elif extra:
     assert out["scaling"] == "strong" and out["config"]["trajectories"] == 6
     assert out["config"]["trajectories_per_gpu"] == 3
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, pkg, tmp_path):
+  """The plain run (no --full): the headline fields, with what takes runs of its own (CPU
+  baselines, stream-copy probe, margin check) absent or null; --dump-outputs writes the last
+  timed step's indicator, adjoint state and refine decision as float64 .npy, equal bit for bit
+  to the same sweep + refine decision run here through the library."""
+  import numpy as np
+  import torch
+  K, nsteps = 65536, 20
+  out = _run(["--gpus", "1", "--K", str(K), "--steps", "2", "--warmup", "1", "--no-converge",
+              "--dump-outputs", str(tmp_path)])
+  assert out["steps"] == 2 and out["warmup_effective"] == 1 and out["ms_per_step"] > 0
+  assert out["unit"] == "DOF-updates/s" and out["higher_is_better"] and out["dtype"] == "f64"
+  # ms_per_step is one timed step: value = the step's DOF-updates over it
+  rate = 2 * 5 * K * nsteps / (out["ms_per_step"] * 1e-3)
+  assert abs(out["value"] - rate) <= 1e-9 * rate
+  assert not any(k.startswith("cpu_baseline") for k in out)
+  assert out["refine_decision"] is None and out["stream_copy"]["achievable_GBs"] is None
+  assert out["dumped_outputs"] == {"eta": [K, K], "refine": [2, 2], "w": [5 * K, 5 * K]}
+  assert sorted(os.listdir(tmp_path)) == ["eta.npy", "refine.npy", "w.npy"]
+  eta, w, ref = (np.load(tmp_path / f"{n}.npy") for n in ("eta", "w", "refine"))
+  assert eta.dtype == w.dtype == ref.dtype == np.float64
+  assert int(ref[0]) == out["refine_index"] and ref[1] == out["refine_value"]
+  ens = pkg.ensemble
+  mesh = pkg.BaseGalerkin1D(n=4, k=K, domain=[0.0, 1.0])
+  sweep = ens.EnsembleSweep(mesh, [0], nsteps, mesh.cfl_dt(),
+                            params=(np.array([1.0]), np.array([1.0]), np.array([0.0])))
+  reducer = ens.DeviceReducer(sweep.op)
+  sweep.sweep_refine(reducer)
+  torch.cuda.synchronize()
+  assert np.array_equal(eta, sweep.eta.cpu().numpy())
+  assert np.array_equal(w, sweep.w.reshape(-1).cpu().numpy())
+  assert int(ref[0]) == int(reducer.idx.item()) and ref[1] == float(reducer.value.item())
