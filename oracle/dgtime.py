@@ -13,6 +13,15 @@ Two behaviours of the reference are kept as written:
 * adj_march.m:73 sets hk = x(1) - x(end) < 0, so its quadrature points
   r_interp = t_a + (1+r) hk/2 (adj_march.m:78) lie in [t_a - h, t_a], before the slab, and
   the mass terms carry the negative hk.
+
+Accuracy (oracle/dgtime_mp.py, the same marches at 50 digits; floors (a)/(b) of
+tests/golden/dgtime_mp_golden.json): the forward march is within 8e-15 of it up to N = 8.
+The adjoint's V / err drift from 4e-14 / 1.5e-13 (N = 1) to 8e-10 / 2e-9 (N = 7), and the
+nodal-form restatement below (dg_march_nodal / adj_march_nodal) drifts by the same amounts:
+neither polyfit nor the nodal form is the side in error at N >= 6.  Both inherit the 5e-15
+of their fp64 forward march (it traces to the fp64 stiffness (V V')\\Dr), which the
+evaluation before the slab multiplies by max|Pext| (2 at N = 1, 2e4 at N = 7).  Past
+N = 4 this oracle is therefore no arbiter for the adjoint at the suite's 1e-10.
 """
 import math
 
@@ -122,6 +131,73 @@ def adj_march(Na, times, y1, t1, y0=1.0):
     A = -S.T - B  # :115
     err[k] = v_k @ (-A @ uh_k - M_tilde + F)  # :117
   return t, v, err
+
+
+def slab_width(ta, tb):
+  """x(end) - x(1) of fem_setup on [ta, tb] (StartUp1D.m:21: x = VX(1) + (r+1)/2 (VX(2)-VX(1)))."""
+  ta, tb = float(ta), float(tb)
+  return (ta + (tb - ta)) - ta
+
+
+def _nodal_quad(Pe, Pa, w, U):
+  ur = Pe @ U
+  return Pa.T @ (w * np.sin(ur)), Pa.T @ ((w * np.cos(ur))[:, None] * Pa)
+
+
+def dg_march_nodal(ops, times, y0, tol=1e-7, maxit=500):
+  """dg_march above with the slab polynomial in the nodal form the kernels use (Phi U in
+  place of polyfit/polyval), fed the operator arrays ops = dict(S, Phi, wq) the package's
+  dgtime.forward_ops hands the device.  Returns (Y, iterations)."""
+  S, Phi, w = (np.asarray(ops[k], dtype=float) for k in ("S", "Phi", "wq"))
+  Np = S.shape[0]
+  A = S.T.copy()
+  A[-1, -1] += -1.0
+  Y, its = [], []
+  uR = float(y0)
+  for k in range(len(times) - 1):
+    hh = 0.5 * slab_width(times[k], times[k + 1])
+    U = uR * np.ones(Np)
+    F = np.zeros(Np)
+    F[0] = uR
+    it, err = 0, 1.0
+    while it <= maxit and err > tol:
+      Mt, J = _nodal_quad(Phi, Phi, w, U)
+      Un = U - np.linalg.solve(A + hh * J, A @ U + hh * Mt + F)
+      err = float(np.linalg.norm(U - Un))
+      U = Un
+      it += 1
+    Y.append(U)
+    its.append(it)
+    uR = U[-1]
+  return Y, its
+
+
+def adj_march_nodal(ops, times, Y, y0):
+  """adj_march above in the nodal form, fed ops = dict(Sa, Ma, Phia, Pext, Ifa, wq) of the
+  package's dgtime.adjoint_ops.  Returns (V, err)."""
+  Sa, Ma, Phia, Pext, Ifa, w = (np.asarray(ops[k], dtype=float)
+                                for k in ("Sa", "Ma", "Phia", "Pext", "Ifa", "wq"))
+  NA = Sa.shape[0]
+  Ks = len(times) - 1
+  V, err = [None] * Ks, np.zeros(Ks)
+  B1 = np.zeros((NA, NA))
+  B1[0, 0] = -1.0
+  B2 = np.zeros((NA, NA))
+  B2[-1, -1] = -1.0
+  vL = 0.0
+  for k in range(Ks - 1, -1, -1):
+    U = np.asarray(Y[k], dtype=float)
+    hh = -0.5 * slab_width(times[k], times[k + 1])
+    Mt, Mv = _nodal_quad(Pext, Phia, w, U)
+    F = hh * (Ma @ np.ones(NA))
+    F[-1] -= vL
+    v = np.linalg.solve(-Sa.T + B1 - hh * Mv, F)
+    vL = v[0]
+    F2 = np.zeros(NA)
+    F2[0] = y0 if k == 0 else Y[k - 1][-1]
+    V[k] = v
+    err[k] = v @ (-(-Sa.T - B2) @ (Ifa @ U) - hh * Mt + F2)
+  return V, err
 
 
 def refine(times, err):
