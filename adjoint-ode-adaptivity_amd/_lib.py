@@ -38,6 +38,7 @@ DG_LIMIT_NONE, DG_LIMIT_EACH_STAGE, DG_LIMIT_PI1_EACH_STAGE = 0, 1, 2
 DG_ADJ_ETA_ASSIGN, DG_ADJ_ETA_ABS = 1, 2
 DG_ADJ_P_TERMINAL_PROLONG = 8
 DG_SWEEP_TERMINAL_STATE = 4
+DG_RESNET_MAX_LAYERS = 256
 
 _c_dbl_p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
@@ -108,6 +109,12 @@ SIGNATURES = {
     "dg_time_adjoint": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp,
                                _vp, _vp, _vp, _vp]),
     "dg_fd_adapt_sweep": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    # offsets (argument 3 / 2 / 2) is a host int32 array
+    "dg_resnet_adapt_sweep": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _i64, _vp, _vp, _vp, _vp]),
+    "dg_resnet_grad_scratch": (_i32, [_i32, _vp, _i64, ctypes.POINTER(_i64)]),
+    "dg_resnet_loss_grad": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                   _vp, _i64, _vp]),
 }
 
 

@@ -10,6 +10,7 @@
 // Layouts: U[n*n_ics + ic] (coarse nodes), V[n*n_ics + ic] (fine nodes, optional),
 // err_steps[ic*n_steps + r] (steps contiguous per member, for dg_sum_rows).
 #include "dg_common.h"
+#include "dg_interp.h"
 
 namespace {
 using namespace dgk;
@@ -17,17 +18,7 @@ using namespace dgk;
 constexpr int kFdBlock = 256;
 constexpr int kMaxRf = 16;  // ref_factor bound (one kernel per value, window in registers)
 
-// np.interp(t_fine[i], t_coarse, u) with numpy's case split (numpy/core/src/multiarray/
-// compiled_base.c arr_interp): code >= 0 -> slope*(x - xp[j]) + fp[j] in interval j,
-// code < 0 -> the coarse node -(code+1) exactly.
-__device__ __forceinline__ double fine_u(int32_t code, double x, const double* __restrict__ tc,
-                                         const double* __restrict__ U, int64_t n_ics,
-                                         int64_t ic) {
-  if (code < 0) return U[int64_t(-(code + 1)) * n_ics + ic];
-  const double u0 = U[int64_t(code) * n_ics + ic], u1 = U[int64_t(code + 1) * n_ics + ic];
-  const double slope = __ddiv_rn(__dsub_rn(u1, u0), __dsub_rn(tc[code + 1], tc[code]));
-  return __dadd_rn(__dmul_rn(slope, __dsub_rn(x, tc[code])), u0);
-}
+// fine_u: np.interp(t_fine[i], t_coarse, u) with numpy's case split (dg_interp.h).
 
 // np.sum(err_steps, 1) over one window (Main_finite_difference.py:276): on that strided
 // 2-D view numpy reduces the last axis sequentially from the window's first element

@@ -550,6 +550,47 @@ int dg_fd_adapt_sweep(int n_steps, int ref_factor, const double* dt_n, const dou
                       const double* t_fine, const int32_t* interp_code, const double* u0,
                       int64_t n_ics, double* U, double* V, double* err_steps, void* stream);
 
+/* ---- ResNet-as-ODE ensemble (python/Main_width_ref.py with scalar state) ----
+ * Layer l is ResBlockSimple (python/models.py:60-64) with F_l neurons,
+ *   Phi_l(u, dt) = u + dt * sum_f W2_l[f] * relu(W1_l[f] * (u - b_l[f])),
+ * its parameters packed in three device arrays bias / w1 / w2 [P] at [offsets[l], offsets[l+1])
+ * (P = offsets[n_layers]).  offsets [n_layers+1] is the one HOST array of these entries: it
+ * is checked here (offsets[0] = 0, strictly increasing) and handed to the kernels by value. */
+enum { DG_RESNET_MAX_LAYERS = 256 };
+
+/* One adapt sweep for n_ics members (initial value u0[ic], label target[ic]), one member per
+ * lane, in one launch: forwardSolve on the n_layers coarse steps dt_n (Main_width_ref.py:48-68);
+ * adjointSolve on the ref_factor-refined grid (:77-105), whose double loop is the backward
+ * recursion v[nf] = sign(u_fine[nf] - target), v[n-1] = v[n] * dPhi/du(u_fine[n-1]) with the
+ * parameters of layer (n-1)/ref_factor and relu'(0) = 0, because forwardFn reads only u[-1];
+ * errorIndicator (:126-139): err[i] = | sum_{n = i*rf+1}^{(i+1)*rf} res[n] * v[n] |,
+ * res[n] = u_fine[n] - Phi(u_fine[n-1], dt_fine[n-1]).  u_fine is the np.interp of the coarse
+ * solution (refineSolution, :117-122): t_coarse, t_fine and interp_code as for
+ * dg_fd_adapt_sweep.  ref_factor 2..16.  Outputs: U[n*n_ics + ic] (coarse solution),
+ * V (nullable) [n*n_ics + ic] (fine adjoint), err_steps[ic*n_layers + i] (for dg_sum_rows:
+ * the mean over members of :479). */
+int dg_resnet_adapt_sweep(int n_layers, int ref_factor, const int32_t* offsets,
+                          const double* bias, const double* w1, const double* w2,
+                          const double* dt_n, const double* t_coarse, const double* t_fine,
+                          const int32_t* interp_code, const double* u0, const double* target,
+                          int64_t n_ics, double* U, double* V, double* err_steps, void* stream);
+
+/* *bytes = the size of the caller-owned device scratch dg_resnet_loss_grad needs for this net
+ * and ensemble size (16-byte aligned; its contents need not be kept between calls). */
+int dg_resnet_grad_scratch(int n_layers, const int32_t* offsets, int64_t n_ics, int64_t* bytes);
+
+/* lossFn (Main_width_ref.py:142-145) per member, loss_ic[ic] = (u_L - target)^2 (nullable), and
+ * trainStep's means over members (:164-169): *loss_mean (device) and grad [3][P] (device; rows
+ * bias, w1, w2 in the packed layout), by backpropagation through the layers.  The member sums
+ * are bit-reproducible (no floating-point atomics): members are cut into chunks of 256 in
+ * ascending order; a chunk's gradient terms are added in ascending member order (its losses by
+ * a stride-halving tree: 128, 64, .., 1); the chunk sums are added in ascending chunk order;
+ * one division by n_ics follows. */
+int dg_resnet_loss_grad(int n_layers, const int32_t* offsets, const double* bias,
+                        const double* w1, const double* w2, const double* dt_n, const double* u0,
+                        const double* target, int64_t n_ics, double* loss_ic, double* loss_mean,
+                        double* grad, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
