@@ -188,8 +188,11 @@ def rel(x, ref):
 
 
 # The input sets of tests/test_gpu_resnet_ensemble.py: name -> (seed, widths, members,
-# ref_factors).  tests/test_resnet_host.py checks the conditioning of every one of them on the
-# CPU; the seeds were chosen so that they pass.
+# ref_factors[, T]).  tests/test_resnet_host.py checks the conditioning of every one of them on
+# the CPU; the seeds were chosen so that they pass.  "wide129" has layers wider than the 128
+# lanes k_resnet_grad_b strides over; "deep256" has DG_RESNET_MAX_LAYERS layers (on [0, 32]: on
+# [0, 1] its 256 residuals are differences of nearly equal states and the oracle's own rounding
+# in err exceeds 1e-12).
 CASES = {
     "main": (0, (5, 7, 4), 4097, (4,)),
     "wide": (3, (100, 100), 1025, (4,)),
@@ -199,6 +202,8 @@ CASES = {
     "edge255": (0, (5, 7, 4), 255, (4,)),
     "edge256": (0, (5, 7, 4), 256, (4,)),
     "edge257": (0, (5, 7, 4), 257, (4,)),
+    "wide129": (1, (129, 300), 513, (4,)),
+    "deep256": (8, (2,) * 256, 300, (4,), 32.0),
 }
 ADAPT_ITERATIONS = 5
 TRAIN_EPOCHS = 5
@@ -208,6 +213,6 @@ _cases = {}
 def case(name):
   """(times, params, u0, target) of CASES[name], built once."""
   if name not in _cases:
-    seed, widths, n_ics, _ = CASES[name]
-    _cases[name] = make_case(seed, widths, n_ics)
+    seed, widths, n_ics, _, *horizon = CASES[name]
+    _cases[name] = make_case(seed, widths, n_ics, *horizon)
   return _cases[name]

@@ -48,7 +48,8 @@ def check_sweep(name, rf, U, V, err):
 
 
 @pytest.mark.parametrize("name,rf", [("main", 4), ("wide", 4), ("rf", 2), ("rf", 3), ("rf", 16),
-                                     ("one_layer", 4), ("one_member", 4)])
+                                     ("one_layer", 4), ("one_member", 4), ("wide129", 4),
+                                     ("deep256", 4)])
 def test_every_member_matches_the_oracle(pkg, gpu, name, rf):
   assert rf in ro.CASES[name][3]
   U, V, err = (t.cpu().numpy() for t in ensemble(pkg, name, rf).sweep(with_v=True))
@@ -171,7 +172,7 @@ def test_depth_adaptation_follows_the_oracle_loop(pkg, gpu):
       np.testing.assert_array_equal(x, y)  # the inserted layers are copies
 
 
-@pytest.mark.parametrize("name", ["main", "one_member"])
+@pytest.mark.parametrize("name", ["main", "one_member", "wide129", "deep256"])
 def test_loss_and_gradient_match_the_oracle_and_repeat_bit_for_bit(pkg, gpu, name):
   ref_loss, ref_grads, ref_ic = ro.loss_grad(*ro.case(name))
   ens = ensemble(pkg, name)

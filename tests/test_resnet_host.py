@@ -155,7 +155,7 @@ def test_gpu_adapt_inputs_are_well_conditioned():
   assert len(its[-1]["params"]) == 3 + ro.ADAPT_ITERATIONS
 
 
-@pytest.mark.parametrize("name", ["main", "one_member"])
+@pytest.mark.parametrize("name", ["main", "one_member", "wide129", "deep256"])
 def test_gpu_gradient_inputs_are_well_conditioned(name):
   times, params, u0, target = ro.case(name)
   loss, grads, _ = ro.loss_grad(times, params, u0, target)
