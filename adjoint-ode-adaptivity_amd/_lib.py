@@ -39,6 +39,7 @@ DG_ADJ_ETA_ASSIGN, DG_ADJ_ETA_ABS = 1, 2
 DG_ADJ_P_TERMINAL_PROLONG = 8
 DG_SWEEP_TERMINAL_STATE = 4
 DG_RESNET_MAX_LAYERS = 256
+DG_MARK_TOP_COUNT, DG_MARK_MAX_FRACTION = 0, 1
 
 _c_dbl_p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
@@ -58,6 +59,9 @@ SIGNATURES = {
     "dg_plan_set_tvb": (_i32, [_vp, ctypes.c_double]),
     "dg_plan_reserve": (_i32, [_vp, _i64]),
     "dg_plan_refine": (_i32, [_vp, _vp, _vp, _vp]),
+    "dg_plan_mark": (_i32, [_vp, _vp, _i32, ctypes.c_double, _i64, _vp, _vp, _vp]),
+    "dg_plan_refine_marked": (_i32, [_vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "dg_plan_query_mark": (_i32, [_vp, ctypes.POINTER(_i64)]),
     "dg_plan_get_mesh": (_i32, [_vp, _c_dbl_p]),
     "dg_advec_rhs": (_i32, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "dg_lserk4_fwd": (_i32, [_vp, _vp, ctypes.c_double, ctypes.c_double, _i32, _vp, _vp]),

@@ -37,10 +37,21 @@ class AdaptiveSweep:
     max_refinements: how many splits the buffers are sized for.
     flux, limiter, a, inflow: the plan's physics (config 3: "burgers", True).
     ic: (amplitude, frequency, phase) of u0 = A sin(2 pi m x + phi).
+    marking: None (one split per iteration: argmax |eta|, the reference's step), ("top", m)
+      (the m worst elements) or ("max", theta) (every element with |eta_k| >= theta max|eta|),
+      see :meth:`~.operators.DGAdvection1D.mark`.  A marked iteration never splits more
+      elements than the buffers still hold; ``iterate`` then returns ``(dofs, n_split)`` and
+      ``history`` records the number of splits.
   """
 
   def __init__(self, mesh, nsteps, max_refinements, a=2 * np.pi, inflow="a", flux="burgers",
-               limiter=True, cfl=0.75, ic=(1.0, 1.0, 0.0), t0=0.0):
+               limiter=True, cfl=0.75, ic=(1.0, 1.0, 0.0), t0=0.0, marking=None):
+    if marking is not None:
+      strategy, param = marking
+      if strategy not in ("top", "max"):
+        raise ValueError(f'marking must be None, ("top", m) or ("max", theta), got {marking!r}')
+      marking = (strategy, float(param))
+    self.marking = marking
     self.nsteps = int(nsteps)
     self.cfl = float(cfl)
     self.t0 = float(t0)
@@ -62,6 +73,10 @@ class AdaptiveSweep:
     self.h_min = float(np.min(np.diff(mesh.v_x)))
     self._length = float(np.max(np.abs(mesh.v_x)))
     self.history = []
+    self.k_cap = k_cap
+    if marking is not None:
+      self._marks = torch.zeros(k_cap, dtype=torch.uint8, device=dev)
+      self._info = torch.zeros(4, dtype=torch.int64, device=dev)
 
   @property
   def K(self):
@@ -107,11 +122,25 @@ class AdaptiveSweep:
                     self.nsteps, eta=eta, eta_assign=True, decisions=self.decisions())
     return eta
 
+  def _room(self):
+    """Splits the buffers still hold; raises when there is none (marking only)."""
+    room = self.k_cap - self.op.K
+    if room <= 0:
+      raise RuntimeError(f"no capacity left to refine: the buffers hold {self.k_cap} "
+                         f"elements (max_refinements) and the mesh has {self.op.K}")
+    return room
+
   def refine(self):
     """argmax |eta| and the device split; returns the DOF-updates of the iteration's sweeps
     (2 Np K nsteps on the mesh they ran on).  Asynchronous: call ``sync`` before the next
     iteration needs the step size."""
     dofs = 2 * self.op.Np * self.op.ktot * self.nsteps
+    if self.marking is not None:
+      room = self._room()
+      # the cap keeps the marked splits within the reserve; the split itself waits for sync()
+      self.op.mark(self.eta(), self.marking[0], self.marking[1], max_marked=room,
+                   marks=self._marks[:self.op.K], info=self._info)
+      return dofs
     self.op.argmax_async(self.eta(), use_abs=True, out=self.idx)
     # argmax puts NaN (and |inf|) first, so eta at the refine index is finite iff all are
     self._eta_at = self._eta.index_select(0, self.idx)
@@ -119,7 +148,11 @@ class AdaptiveSweep:
     return dofs
 
   def sync(self):
-    """Bring the refine index and the split width to the host; update h_min."""
+    """Bring the refine index and the split width to the host; update h_min.  With a marking
+    strategy: read the mark pass's counts once, raise on a non-finite indicator before any
+    split, split the marked elements and return their number."""
+    if self.marking is not None:
+      return self._sync_marked()
     idx = int(self.idx.item())
     check_indicator(float(self._eta_at.item()), idx)
     h_new = 0.5 * float(self.h_split.item())
@@ -130,7 +163,26 @@ class AdaptiveSweep:
     self.history.append(idx)
     return idx
 
+  def _sync_marked(self):
+    count, nonfinite, width_bits, _ = self._info.tolist()
+    if nonfinite > 0:
+      raise FloatingPointError(f"non-finite DWR indicator in {nonfinite} element(s): the "
+                               "forward or adjoint sweep diverged")
+    if count > 0:
+      h_new = 0.5 * float(np.int64(width_bits).view(np.float64))
+      if not h_new > 64 * np.finfo(np.float64).eps * self._length:
+        raise FloatingPointError(f"refining the {count} marked elements would leave elements "
+                                 f"of width {h_new:g}: the split has reached fp64 resolution "
+                                 "of the coordinates")
+    _, n_split = self.op.refine_marked(self._marks[:self.op.K])
+    if n_split > 0:
+      self.h_min = min(self.h_min, h_new)
+    self.history.append(n_split)
+    return n_split
+
   def iterate(self):
+    if self.marking is not None:
+      self._room()  # fail before the sweeps, not after them
     dt = self.dt
     self.forward(dt)
     self.adjoint(dt)

@@ -1273,6 +1273,7 @@ int dg_plan_create(int N, int64_t K, int64_t batch, const double* r, const doubl
     return cleanup("hipMalloc scratch2");
   if (hipMalloc(&p->d_pv, sizeof(double) * kArgmaxParts) != hipSuccess) return cleanup("hipMalloc pv");
   if (hipMalloc(&p->d_pi, sizeof(int64_t) * kArgmaxParts) != hipSuccess) return cleanup("hipMalloc pi");
+  if (hipMalloc(&p->d_mark, kMarkBytes) != hipSuccess) return cleanup("hipMalloc mark");
   if (hipMemcpy(p->d_scale, scale.data(), sizeof(double) * K, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(p->d_VX, VX, sizeof(double) * (K + 1), hipMemcpyHostToDevice) != hipSuccess) {
     dg_plan_destroy(p);
@@ -1290,6 +1291,7 @@ int dg_plan_destroy(dg_plan* p) {
   if (p->d_scratch2) (void)hipFree(p->d_scratch2);
   if (p->d_pv) (void)hipFree(p->d_pv);
   if (p->d_pi) (void)hipFree(p->d_pi);
+  if (p->d_mark) (void)hipFree(p->d_mark);
   if (p->d_sweep || !p->sweep_retired.empty()) (void)hipDeviceSynchronize();
   if (p->d_sweep) (void)hipFree(p->d_sweep);
   for (void* q : p->sweep_retired) (void)hipFree(q);

@@ -97,6 +97,9 @@ __device__ __forceinline__ const DG_KAS char* kernarg_tail_k() {
 // (the dataflow sweeps' block tables) check their argument struct against it at compile time.
 constexpr size_t kKernargMax = 4096;
 
+// Bytes of the plan's marking state (dg_mark.hip: MarkState + one histogram per select pass).
+constexpr size_t kMarkBytes = 16384;
+
 // Sets the calling thread's dg_last_error() text and returns `code` (dg_advec.hip).
 int fail(int code, const std::string& msg);
 
@@ -442,6 +445,9 @@ struct dg_plan {
   double* d_scratch2 = nullptr;
   double* d_pv = nullptr;
   int64_t* d_pi = nullptr;
+  // dg_plan_mark / dg_plan_refine_marked (dg_mark.hip): the select's state words and digit
+  // histograms (dgk::kMarkBytes, fixed size; the per-workgroup sums live in d_scratch2)
+  void* d_mark = nullptr;
   // tuning (dg_plan_tune): tile width of the step kernels (tile = 256*tile_width elements)
   int tile_width = 1;  // dg_plan_create: 2 for N <= 2 (measured per-N)
   int msteps = 4;  // time steps fused per launch (1, 2 or 4)

@@ -12,6 +12,8 @@ LSERK4 loop, One_code.mlx:106-140   ``op.forward(u, t0, dt, nsteps, snapshots)``
 ``SlopeLimitN(u)``                  ``op.slope_limit(u)``      (utils/SlopeLimitN.m:1)
 ``argmax(err)`` (:337)              ``op.argmax(eta, use_abs=True)``
 split of :336-341 / MAIN.m:137-141  ``op.refine(idx)`` (on the device)
+the same for a set of elements      ``op.mark(eta, "top" | "max", param)`` then
+                                    ``op.refine_marked(marks)``
 =================================  ===============================================
 
 ``flux="burgers"`` and/or ``limiter=True`` select the config-3 physics (BASELINE.json
@@ -36,6 +38,7 @@ SCHEME = {"lserk4": _lib.DG_TIME_LSERK4, "euler": _lib.DG_TIME_EULER}
 FLUX = {"linear": _lib.DG_FLUX_LINEAR, "burgers": _lib.DG_FLUX_BURGERS}
 LIMITER = {False: _lib.DG_LIMIT_NONE, True: _lib.DG_LIMIT_EACH_STAGE,
            "N": _lib.DG_LIMIT_EACH_STAGE, "1": _lib.DG_LIMIT_PI1_EACH_STAGE}
+MARK = {"top": _lib.DG_MARK_TOP_COUNT, "max": _lib.DG_MARK_MAX_FRACTION}
 
 
 def _stream(device):
@@ -223,6 +226,57 @@ class DGAdvection1D:
     _lib.check(rc, "dg_plan_refine")
     self._query()
     return self.K
+
+  def query_mark(self):
+    """(elements per workgroup of the marking passes, per-workgroup sums the scanning
+    workgroup consumes per iteration, key bits per select pass) — dg_plan_query_mark."""
+    q = (ctypes.c_int64 * 4)()
+    _lib.check(self._lib.dg_plan_query_mark(self._plan, q), "dg_plan_query_mark")
+    return int(q[0]), int(q[1]), int(q[2])
+
+  def mark(self, eta, strategy, param, max_marked=None, marks=None, info=None):
+    """Choose the elements to refine from the length-K indicator ``eta`` (dg_plan_mark).
+
+    ``strategy`` "top" (``param`` = m: the m worst elements) or "max" (``param`` = theta: every
+    element with |eta_k| >= theta * max|eta|), ranked by ``argmax``'s order (NaN first, ties to
+    the lower index); ``max_marked`` caps the marked set (None: no cap).  Returns ``(marks,
+    info)``: CUDA uint8[K] of 0/1 and CUDA int64[4] = (count marked, count of non-finite
+    entries, bits of the minimum marked width, 0).  Asynchronous."""
+    if strategy not in MARK:
+      raise ValueError(f"strategy must be one of {sorted(MARK)}, got {strategy!r}")
+    marks = (torch.empty(self.K, dtype=torch.uint8, device=self.device) if marks is None
+             else marks)
+    info = torch.empty(4, dtype=torch.int64, device=self.device) if info is None else info
+    rc = self._lib.dg_plan_mark(self._plan, self._field(eta, "eta", self.K), MARK[strategy],
+                                float(param), -1 if max_marked is None else int(max_marked),
+                                self._field(marks, "marks", self.K, torch.uint8),
+                                self._field(info, "info", 4, torch.int64),
+                                _stream(self.device))
+    _lib.check(rc, "dg_plan_mark")
+    return marks, info
+
+  def refine_marked(self, marks, parent=None):
+    """Split every element with a nonzero mark at its midpoint on the device
+    (dg_plan_refine_marked; Main_finite_difference.py:336-341 for a set of elements).
+    ``parent`` (CUDA int32, at least K + splits elements, optional) receives each new
+    element's old index.  Synchronises; returns ``(K_new, n_split)``."""
+    mp = self._field(marks, "marks", self.K, torch.uint8)
+    pp = None
+    if parent is not None:
+      if (not isinstance(parent, torch.Tensor) or not parent.is_cuda
+          or parent.dtype != torch.int32 or not parent.is_contiguous()):
+        raise TypeError("parent must be a contiguous CUDA int32 tensor")
+      n_marked = int(torch.count_nonzero(marks).item())
+      if parent.numel() < self.K + n_marked:
+        raise ValueError(f"parent has {parent.numel()} elements, the refined mesh "
+                         f"{self.K + n_marked}")
+      pp = ctypes.c_void_p(parent.data_ptr())
+    n = ctypes.c_int64(0)
+    rc = self._lib.dg_plan_refine_marked(self._plan, mp, pp, ctypes.byref(n),
+                                         _stream(self.device))
+    _lib.check(rc, "dg_plan_refine_marked")
+    self._query()
+    return self.K, int(n.value)
 
   def v_x(self):
     """The plan's current vertex coordinates (host copy; synchronises)."""

@@ -228,6 +228,50 @@ int dg_plan_reserve(dg_plan* plan, int64_t K_capacity);
  * is modified, so it must not be used concurrently. */
 int dg_plan_refine(dg_plan* plan, const int64_t* idx, double* h_split, void* stream);
 
+/* Marking: choose a SET of elements to refine from a length-K indicator eta (device; one value
+ * per element of the plan's shared mesh: a batched caller reduces with dg_sum_rows first).
+ * Generalises the one-element decision of python/Main_finite_difference.py:336-341 (argmax of
+ * err_contribution) and matlab/MAIN.m:137-141.  Everything ranks by dg_argmax(use_abs = 1)'s
+ * total order: the key of x is the 64 bits of |x| read as an unsigned integer (-0 == +0, +inf
+ * above every finite value), NaN's key is all ones (NaN first, numpy's argmax), a larger key
+ * ranks first, equal keys by the lower index.
+ *   DG_MARK_TOP_COUNT     param = m >= 0 (integral): the first min(m, K, max_marked) elements in
+ *                         rank order (m = 1: exactly dg_argmax's element)
+ *   DG_MARK_MAX_FRACTION  param = theta in (0, 1]: with M the top-ranked |eta|, the candidates
+ *                         are {k : |eta_k| >= theta*M and |eta_k| > 0} when M is finite (theta*M
+ *                         one fp64 product; an all-zero indicator marks nothing) and exactly the
+ *                         non-finite entries otherwise; more candidates than max_marked: the
+ *                         top max_marked of them in rank order
+ * marks (device uint8[K]) is fully written with 0 or 1.  info (device or mapped page-locked
+ * int64[4]) = the count marked, the count of non-finite entries of eta, the bits of the minimum
+ * width VX[k+1] - VX[k] over marked elements (+inf when none is marked), 0.  max_marked < 0: no
+ * cap.  The selection is an exact radix select with integer atomics only: the same input gives
+ * the same bits on every run.  Asynchronous on stream; uses the plan's scratch, so the plan
+ * must not be used concurrently.  DG_ERR_ARG: a null pointer, an unknown strategy, m < 0 or
+ * non-integral, theta outside (0, 1] or NaN. */
+enum { DG_MARK_TOP_COUNT = 0, DG_MARK_MAX_FRACTION = 1 };
+int dg_plan_mark(dg_plan* plan, const double* eta, int strategy, double param,
+                 int64_t max_marked, uint8_t* marks, int64_t* info, void* stream);
+
+/* Refine every marked element on the device: element k with marks[k] != 0 (device uint8[K],
+ * e.g. dg_plan_mark's output) is split at its midpoint — the split of
+ * python/Main_finite_difference.py:336-341 and matlab/MAIN.m:137-141, applied to all marked
+ * elements at once, with midpoint and metrics computed by dg_plan_refine's expressions; an
+ * unmarked element keeps its metric bit for bit.  parent (nullable, device int32[K + splits])
+ * receives each new element's old index, to carry per-element data across the refinement;
+ * n_split (nullable, host) the number of splits.  SYNCHRONOUS: it scans the marks and reads
+ * their total back to the host before it touches the mesh, so it is not capturable in a HIP
+ * graph.  K + total > capacity (dg_plan_reserve): DG_ERR_ARG with the mesh untouched.  Otherwise
+ * K grows by the total and the mesh is non-uniform from then on, as after dg_plan_refine; with
+ * no marks the plan is unchanged (a uniform plan stays uniform). */
+int dg_plan_refine_marked(dg_plan* plan, const uint8_t* marks, int32_t* parent, int64_t* n_split,
+                          void* stream);
+
+/* The marking kernels' geometry: out[0] = elements per workgroup of the histogram / scan
+ * passes, out[1] = per-workgroup sums the single scanning workgroup consumes per iteration,
+ * out[2] = key bits settled per select pass, out[3] = 0. */
+int dg_plan_query_mark(const dg_plan* plan, int64_t out[4]);
+
 /* Copy the plan's current K+1 vertex coordinates to the host array VX (synchronous). */
 int dg_plan_get_mesh(const dg_plan* plan, double* VX);
 
