@@ -62,6 +62,8 @@ SIGNATURES = {
     "dg_plan_mark": (_i32, [_vp, _vp, _i32, ctypes.c_double, _i64, _vp, _vp, _vp]),
     "dg_plan_refine_marked": (_i32, [_vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
     "dg_plan_query_mark": (_i32, [_vp, ctypes.POINTER(_i64)]),
+    "dg_field_to_children": (_i32, [_vp, _vp, _i64, _c_dbl_p, _vp, _vp, _vp]),
+    "dg_field_from_children": (_i32, [_vp, _vp, _i64, _c_dbl_p, _vp, _vp, _vp]),
     "dg_plan_get_mesh": (_i32, [_vp, _c_dbl_p]),
     "dg_advec_rhs": (_i32, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "dg_lserk4_fwd": (_i32, [_vp, _vp, ctypes.c_double, ctypes.c_double, _i32, _vp, _vp]),

@@ -11,6 +11,10 @@ matlab/MAIN.m:29-141) on the DG mesh, with every array kept in HBM:
 The only host traffic per iteration is the refine index and the split element's width
 (the next step size follows the CFL rule of utils/One_code.mlx:111-112 on the refined
 mesh).  Buffers are sized once for ``max_refinements`` splits.
+
+The IC is the analytic sine, re-evaluated on every mesh, or nodal data given on the initial
+mesh, which each refinement carries to the new mesh on the device (dg_field_to_children: the
+interpU role of python/factory.py:281-286).
 """
 import numpy as np
 import torch
@@ -36,7 +40,12 @@ class AdaptiveSweep:
     nsteps: time steps per sweep (each direction).
     max_refinements: how many splits the buffers are sized for.
     flux, limiter, a, inflow: the plan's physics (config 3: "burgers", True).
-    ic: (amplitude, frequency, phase) of u0 = A sin(2 pi m x + phi).
+    ic: (amplitude, frequency, phase) of u0 = A sin(2 pi m x + phi), re-evaluated
+      on every refined mesh; or a CUDA float64 tensor of K0 * Np nodal values in the device
+      layout on the initial mesh (measured data, an earlier sweep's state), which every
+      refinement carries to the new mesh on the device
+      (:meth:`~.operators.DGAdvection1D.transfer`: the same polynomials, unsplit elements bit
+      for bit; ``u0()`` is the carried data on the current mesh).
     marking: None (one split per iteration: argmax |eta|, the reference's step), ("top", m)
       (the m worst elements) or ("max", theta) (every element with |eta_k| >= theta max|eta|),
       see :meth:`~.operators.DGAdvection1D.mark`.  A marked iteration never splits more
@@ -55,11 +64,22 @@ class AdaptiveSweep:
     self.nsteps = int(nsteps)
     self.cfl = float(cfl)
     self.t0 = float(t0)
-    self.ic = tuple(float(v) for v in ic)
+    carried = isinstance(ic, torch.Tensor)
+    self.ic = None if carried else tuple(float(v) for v in ic)
     self.op = DGAdvection1D(mesh, a=a, inflow=inflow, flux=flux, limiter=limiter)
     k_cap = mesh.k + int(max_refinements)
     self.op.reserve(k_cap)
     dev = self.op.device
+    # nodal initial data: two ping-pong buffers of the full capacity and the refinement's map
+    self._carry = None
+    if carried:
+      n0 = self.op.field_numel
+      self.op._field(ic, "ic", n0)  # CUDA float64, contiguous, K0 * Np values
+      self._carry = [torch.zeros(k_cap * mesh.n_p, dtype=torch.float64, device=dev)
+                     for _ in range(2)]
+      self._carry[0][:n0].copy_(ic.reshape(-1))
+      self._cur = 0
+      self._parent = torch.zeros(k_cap, dtype=torch.int32, device=dev)
     self._snaps = torch.empty((self.nsteps + 1) * k_cap * mesh.n_p, dtype=torch.float64,
                               device=dev)
     self._eta = torch.zeros(k_cap, dtype=torch.float64, device=dev)
@@ -97,8 +117,23 @@ class AdaptiveSweep:
   def init_state(self):
     """u^0 = the IC on the current mesh (snapshot 0).  (eta needs no reset: the adjoint's
     first launch assigns it, DG_ADJ_ETA_ASSIGN.)"""
+    if self._carry is not None:
+      self.snapshots()[0].copy_(self.u0())
+      return
     amp, freq, phase = self.ic
     self.op.init_sine([amp], [freq], [phase], out=self.snapshots()[0])
+
+  def u0(self):
+    """The carried nodal initial data on the current mesh (a tensor ``ic`` only)."""
+    if self._carry is None:
+      raise RuntimeError("no carried data: ic is the analytic sine")
+    return self._carry[self._cur][:self.op.field_numel]
+
+  def _carry_over(self, parent, k_old):
+    """Carry the initial data from the k_old-element mesh to the plan's refined mesh."""
+    src = self._carry[self._cur][:k_old * self.op.Np]
+    self._cur ^= 1
+    self.op.transfer(src, parent, k_old, out=self._carry[self._cur][:self.op.field_numel])
 
   def decisions(self):
     return None if self._codes is None else self._codes[:self.nsteps * self.op.ktot]
@@ -144,7 +179,10 @@ class AdaptiveSweep:
     self.op.argmax_async(self.eta(), use_abs=True, out=self.idx)
     # argmax puts NaN (and |inf|) first, so eta at the refine index is finite iff all are
     self._eta_at = self._eta.index_select(0, self.idx)
+    k_old = self.op.K
     self.op.refine(self.idx, self.h_split)
+    if self._carry is not None:  # stays asynchronous: the map comes from the device index
+      self._carry_over(DGAdvection1D.parent_of_split(self.idx, k_old), k_old)
     return dofs
 
   def sync(self):
@@ -174,9 +212,13 @@ class AdaptiveSweep:
         raise FloatingPointError(f"refining the {count} marked elements would leave elements "
                                  f"of width {h_new:g}: the split has reached fp64 resolution "
                                  "of the coordinates")
-    _, n_split = self.op.refine_marked(self._marks[:self.op.K])
+    k_old = self.op.K
+    parent = None if self._carry is None else self._parent
+    _, n_split = self.op.refine_marked(self._marks[:k_old], parent=parent)
     if n_split > 0:
       self.h_min = min(self.h_min, h_new)
+      if parent is not None:
+        self._carry_over(parent[:self.op.K], k_old)
     self.history.append(n_split)
     return n_split
 

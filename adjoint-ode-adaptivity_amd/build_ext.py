@@ -13,7 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(_HERE, "csrc", f) for f in ("dg_advec.hip", "dg_burgers.hip", "dg_burgers_ov.hip", "dg_wave.hip", "dg_time.hip", "dg_fd.hip", "dg_resnet.hip",
                                                      "dg_util.hip", "dg_rec.hip", "dg_dwr.hip",
                                                      "dg_sweep.hip", "dg_sweep_hi.hip",
-                                                     "dg_sweep_ov.hip", "dg_mark.hip")]
+                                                     "dg_sweep_ov.hip", "dg_mark.hip",
+                                                     "dg_transfer.hip")]
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 OUT = os.path.join(_HERE, "lib", "libdgadv.so")
 ARCH = os.environ.get("DG_OFFLOAD_ARCH", "gfx950")

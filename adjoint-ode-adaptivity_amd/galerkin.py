@@ -213,6 +213,24 @@ def prolongation(lo, hi):
   return lo.vandermonde1D(lo.n, hi.r_gl) @ lo.inv_v
 
 
+def split_interpolation(mesh):
+  """(PL, RL) of an element split at its midpoint (the split of
+  python/Main_finite_difference.py:336-341 / matlab/MAIN.m:137-141 applied to a nodal field;
+  dg_field_to_children / dg_field_from_children).
+
+  PL (n_p x n_p): the parent's polynomial evaluated at the left child's nodes, which sit at the
+  parent's reference coordinates (r - 1)/2: Vandermonde1D there times invV.  RL: the left
+  child's block of the L2 projection of the two children onto the parent,
+  RL = M^-1 PL^T M / 2 with the mass matrix M = (V V^T)^-1 (the 1/2 is the children's Jacobian
+  relative to the parent's).  The right child's matrices are J PL J and J RL J with J the node
+  reversal (the LGL nodes are symmetric), and RL PL + RR PR = I."""
+  r = mesh.r_gl
+  pl = mesh.vandermonde1D(mesh.n, 0.5 * (r - 1.0)) @ mesh.inv_v
+  m_inv = mesh.v @ mesh.v.T
+  rl = 0.5 * (m_inv @ pl.T @ np.linalg.inv(m_inv))
+  return pl, rl
+
+
 def split_interval(nodes, idx):
   """Insert the midpoint of interval ``idx`` (0-based) into a sorted node vector —
   the refinement of python/Main_finite_difference.py:336-341 (ref_idx = idx + 1) and

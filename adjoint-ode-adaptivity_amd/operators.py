@@ -14,6 +14,9 @@ LSERK4 loop, One_code.mlx:106-140   ``op.forward(u, t0, dt, nsteps, snapshots)``
 split of :336-341 / MAIN.m:137-141  ``op.refine(idx)`` (on the device)
 the same for a set of elements      ``op.mark(eta, "top" | "max", param)`` then
                                     ``op.refine_marked(marks)``
+``interpU`` (factory.py:281-286)    ``op.transfer(u, parent, k_old)``, its transpose
+                                    ``op.transfer_t`` and the L2 projection
+                                    ``op.restrict`` back to the coarser mesh
 =================================  ===============================================
 
 ``flux="burgers"`` and/or ``limiter=True`` select the config-3 physics (BASELINE.json
@@ -31,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .galerkin import BaseGalerkin1D, prolongation
+from .galerkin import BaseGalerkin1D, prolongation, split_interpolation
 
 INFLOW = {"a": _lib.DG_INFLOW_SIN_AT, "a2": _lib.DG_INFLOW_SIN_A2T, "zero": _lib.DG_INFLOW_ZERO}
 SCHEME = {"lserk4": _lib.DG_TIME_LSERK4, "euler": _lib.DG_TIME_EULER}
@@ -212,7 +215,8 @@ class DGAdvection1D:
   def refine(self, idx, h_split=None):
     """Split element ``idx`` (a 1-element CUDA int64 tensor, e.g. ``argmax_async``'s
     output) at its midpoint on the device (Main_finite_difference.py:336-341,
-    MAIN.m:137-141).  K grows by one; fields of the old size must be re-initialised.
+    MAIN.m:137-141).  K grows by one; fields of the old size are re-initialised or carried
+    over with ``transfer(u, parent_of_split(idx, k_old), k_old)``.
     ``h_split`` (1-element CUDA float64, optional) receives the split element's width."""
     if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int64:
       raise TypeError("idx must be a CUDA int64 tensor")
@@ -277,6 +281,94 @@ class DGAdvection1D:
     _lib.check(rc, "dg_plan_refine_marked")
     self._query()
     return self.K, int(n.value)
+
+  # --- fields across a refinement (dg_field_to_children / dg_field_from_children) ---
+  @staticmethod
+  def parent_of_split(idx, k_old):
+    """The ``parent`` map (int32[k_old + 1], on ``idx``'s device) of ``refine(idx)``'s single
+    split, from the device index: new element n comes from old element n - (n > idx).  torch
+    arithmetic only, no host synchronisation; ``idx`` is clamped to [0, k_old) as
+    dg_plan_refine clamps it."""
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.numel() != 1:
+      raise TypeError("idx must be a 1-element int64 tensor")
+    n = torch.arange(int(k_old) + 1, dtype=torch.int64, device=idx.device)
+    j = idx.reshape(1).clamp(0, int(k_old) - 1)
+    return (n - (n > j).to(torch.int64)).to(torch.int32)
+
+  @staticmethod
+  def check_parent(parent, k_old):
+    """Raise ValueError unless ``parent`` describes one level of midpoint splits of a
+    ``k_old``-element mesh: it starts at 0, ends at k_old - 1, steps by 0 or 1 and repeats no
+    value more than twice.  torch ops on ``parent``'s device (the verdict synchronises)."""
+    if not isinstance(parent, torch.Tensor) or parent.dim() != 1 or parent.is_floating_point():
+      raise TypeError("parent must be a 1-D integer tensor")
+    k_old = int(k_old)
+    if k_old < 1 or parent.numel() < k_old or parent.numel() > 2 * k_old:
+      raise ValueError(f"parent has {parent.numel()} elements: not a one-level refinement of "
+                       f"{k_old} elements")
+    p = parent.to(torch.int64)
+    d = p[1:] - p[:-1]
+    ends = (p[0] == 0) & (p[-1] == k_old - 1)
+    steps = ((d == 0) | (d == 1)).all()
+    twice = ~((d[1:] == 0) & (d[:-1] == 0)).any()
+    ok = [bool(v) for v in torch.stack((ends, steps, twice)).tolist()]
+    if not ok[0]:
+      raise ValueError(f"parent must start at 0 and end at k_old - 1 = {k_old - 1}")
+    if not ok[1]:
+      raise ValueError("parent must step by 0 or 1")
+    if not ok[2]:
+      raise ValueError("parent repeats a value more than twice (one level of splits only)")
+
+  def _split_matrix(self, name):
+    """Host copies of PL, PL^T and RL (galerkin.split_interpolation), kept with the plan."""
+    if not hasattr(self, "_split"):
+      pl, rl = split_interpolation(self.mesh)
+      self._split = {"PL": _lib.dbl_array(pl), "PLT": _lib.dbl_array(pl.T),
+                     "RL": _lib.dbl_array(rl)}
+    return self._split[name][1]
+
+  def _parent(self, parent):
+    if (not isinstance(parent, torch.Tensor) or not parent.is_cuda
+        or parent.dtype != torch.int32 or not parent.is_contiguous()):
+      raise TypeError("parent must be a contiguous CUDA int32 tensor")
+    if parent.numel() != self.K:
+      raise ValueError(f"parent has {parent.numel()} elements, the refined mesh {self.K}")
+    return ctypes.c_void_p(parent.data_ptr())
+
+  def _across(self, fn, matrix, x, name, parent, k_old, out, to_children):
+    k_old = int(k_old)
+    if k_old < 1 or k_old > self.K or self.K > 2 * k_old:
+      raise ValueError(f"k_old = {k_old} is not the element count before one level of splits "
+                       f"(the plan has {self.K})")
+    n_old = self.batch * k_old * self.Np
+    n_in, n_out = (n_old, self.field_numel) if to_children else (self.field_numel, n_old)
+    xp = self._field(x, name, n_in)
+    pp = self._parent(parent)
+    out = torch.empty(n_out, dtype=torch.float64, device=self.device) if out is None else out
+    rc = getattr(self._lib, fn)(self._plan, pp, k_old, self._split_matrix(matrix), xp,
+                                self._field(out, "out", n_out), _stream(self.device))
+    _lib.check(rc, fn)
+    return out
+
+  def transfer(self, u, parent, k_old, out=None):
+    """Prolong: the field ``u`` of the mesh before the refinement (batch * k_old * Np) on this
+    (refined) plan's mesh — the same element polynomials, so exact: unsplit elements are copied
+    bit for bit, a split element's children get PL u / PR u (galerkin.split_interpolation; the
+    interpU role of factory.py:281-286).  ``parent``: CUDA int32[K] as ``refine_marked`` writes
+    it or ``parent_of_split`` builds it.  Asynchronous."""
+    return self._across("dg_field_to_children", "PL", u, "u", parent, k_old, out, True)
+
+  def transfer_t(self, w, parent, k_old, out=None):
+    """The exact transpose of ``transfer``: ``w`` on this plan's mesh to the mesh before the
+    refinement, w_old[k] = w[n] (unsplit) or PL^T w[n] + PR^T w[n + 1] (split): adjoints and
+    gradients taken back across a refinement."""
+    return self._across("dg_field_from_children", "PLT", w, "w", parent, k_old, out, False)
+
+  def restrict(self, u, parent, k_old, out=None):
+    """The L2 projection of ``u`` on this plan's mesh onto the mesh before the refinement:
+    u_old[k] = u[n] (unsplit) or RL u[n] + RR u[n + 1].  ``restrict(transfer(u)) == u`` to
+    rounding, and the mass sum_k h_k/2 1^T M u_k is conserved."""
+    return self._across("dg_field_from_children", "RL", u, "u", parent, k_old, out, False)
 
   def v_x(self):
     """The plan's current vertex coordinates (host copy; synchronises)."""

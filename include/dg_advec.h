@@ -272,6 +272,37 @@ int dg_plan_refine_marked(dg_plan* plan, const uint8_t* marks, int32_t* parent, 
  * out[2] = key bits settled per select pass, out[3] = 0. */
 int dg_plan_query_mark(const dg_plan* plan, int64_t out[4]);
 
+/* Carry a nodal field across ONE level of midpoint splits (dg_plan_refine's or
+ * dg_plan_refine_marked's).  plan: the refined plan (K = K_new); k_old: the element count before
+ * the refinement; parent: device int32[K_new] as dg_plan_refine_marked writes it (nondecreasing
+ * from 0 to k_old - 1, an element that was split appears twice) — it belongs to the mesh, so
+ * every trajectory of the batch uses the same map; A: HOST Np x Np row-major, the left child's
+ * matrix.  The right child's matrix is its image J A J under node reversal (the LGL nodes are
+ * symmetric), so a caller chooses the operator by the one matrix it passes:
+ *   dg_field_to_children    out_new[n] = in_old[parent[n]] for an unsplit element (a copy of the
+ *                           bits: NaN payloads, -0 and +-inf survive), A in_old[parent[n]] for a
+ *                           left child, J A J in_old[parent[n]] for a right child.  With A = PL,
+ *                           the parent's polynomial at the left child's nodes (r - 1)/2, this
+ *                           re-expresses the same polynomial on the finer mesh: the field half
+ *                           of the split of python/Main_finite_difference.py:336-341 /
+ *                           matlab/MAIN.m:137-141, i.e. the interpU role of
+ *                           python/factory.py:281-286.
+ *   dg_field_from_children  out_old[k] = in_new[n] for an unsplit element (a copy of the bits),
+ *                           A in_new[n] + J A J in_new[n + 1] for an element split into n, n + 1.
+ *                           With A = PL^T this is the exact transpose of the above (adjoints and
+ *                           gradients taken back across the split of
+ *                           Main_finite_difference.py:336-341 / MAIN.m:137-141); with
+ *                           A = M^-1 PL^T M / 2 the L2 projection of the children onto the parent
+ *                           (interpU of factory.py:281-286 from the finer to the coarser mesh).
+ * Fields are batch * k_old * Np (old) and batch * K * Np (new) doubles in the device layout.
+ * Elements whose parent lies outside [0, k_old) are neither read nor written.  No atomics: equal
+ * inputs give equal bits.  Asynchronous on stream; no plan scratch is used.  DG_ERR_ARG: a null
+ * pointer; k_old < 1, k_old > K or K > 2 k_old; input and output ranges that overlap. */
+int dg_field_to_children(const dg_plan* plan, const int32_t* parent, int64_t k_old,
+                         const double* A, const double* in_old, double* out_new, void* stream);
+int dg_field_from_children(const dg_plan* plan, const int32_t* parent, int64_t k_old,
+                           const double* A, const double* in_new, double* out_old, void* stream);
+
 /* Copy the plan's current K+1 vertex coordinates to the host array VX (synchronous). */
 int dg_plan_get_mesh(const dg_plan* plan, double* VX);
 
