@@ -1527,6 +1527,8 @@ int dg_plan_refine(dg_plan* p, const int64_t* idx, double* h_split, void* stream
   if (!p || !idx) return fail(DG_ERR_ARG, "null argument");
   if (p->K + 1 > p->K_cap)
     return fail(DG_ERR_ARG, "plan capacity exhausted: call dg_plan_reserve first");
+  if (const int rc = disjoint({{"idx", idx, sizeof(int64_t)}, {"h_split", h_split, sizeof(double)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // The old mesh goes to scratch first (the split shifts it in place).
   double* vx_old = p->d_scratch;
@@ -1551,6 +1553,9 @@ int dg_plan_get_mesh(const dg_plan* p, double* VX) {
 
 int dg_advec_rhs(const dg_plan* p, const double* u, double* rhs, double t, void* stream) {
   if (!p || !u || !rhs) return fail(DG_ERR_ARG, "null argument");
+  // (k_rhs and the Burgers kernel read a neighbour element's face while other lanes store)
+  const size_t fb = sizeof(double) * size_t(p->ktot) * size_t(p->NP);
+  if (const int rc = disjoint({{"u", u, fb}, {"rhs", rhs, fb}})) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (p->flux == DG_FLUX_BURGERS) return nl_rhs(p, u, rhs, t, st);
   const double uin = inflow_value(p, t);
@@ -1574,6 +1579,14 @@ int dg_lserk4_fwd_ex(dg_plan* p, double* u, double t0, double dt, int nsteps, do
   if (nsteps < 0) return fail(DG_ERR_ARG, "nsteps < 0");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t field = p->ktot * p->NP;
+  {  // u == snapshots + 0 is the one alias; the record is written on limited plans only
+    const size_t fb = sizeof(double) * size_t(field);
+    if (const int rc = disjoint({{"u", u == snapshots ? nullptr : u, fb},
+                                 {"snapshots", snapshots, fb * (size_t(nsteps) + 1)},
+                                 {"decisions", p->limiter ? decisions : nullptr,
+                                  sizeof(uint16_t) * size_t(nsteps) * size_t(p->ktot)}}))
+      return rc;
+  }
   if (nsteps == 0) {  // the empty sweep: snapshot 0 still receives u^0
     if (snapshots && snapshots != u)
       HIP_TRY(hipMemcpyAsync(snapshots, u, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
@@ -1648,6 +1661,16 @@ int dg_lserk4_adj_ex(dg_plan* p, double* w, const double* snapshots, double t0, 
   if (nsteps < 0) return fail(DG_ERR_ARG, "nsteps < 0");
   if (flags & ~(DG_ADJ_ETA_ASSIGN | DG_ADJ_ETA_ABS)) return fail(DG_ERR_ARG, "unknown flags");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  {  // w == the terminal snapshot is the one alias
+    const size_t fb = sizeof(double) * size_t(p->ktot) * size_t(p->NP);
+    const bool terminal = w == snapshots + int64_t(nsteps) * p->ktot * p->NP;
+    if (const int rc = disjoint({{"w", terminal ? nullptr : w, fb},
+                                 {"snapshots", snapshots, fb * (size_t(nsteps) + 1)},
+                                 {"eta", eta, sizeof(double) * size_t(p->ktot)},
+                                 {"decisions", p->limiter ? decisions : nullptr,
+                                  sizeof(uint16_t) * size_t(nsteps) * size_t(p->ktot)}}))
+      return rc;
+  }
   if (eta != nullptr && nsteps == 0 && (flags & DG_ADJ_ETA_ASSIGN))  // nothing to assign from
     HIP_TRY(hipMemsetAsync(eta, 0, sizeof(double) * p->ktot, st));
   if (p->nonlinear())
@@ -1701,6 +1724,13 @@ int dg_lserk4_fwd_rec(dg_plan* p, const double* u0, double* uN, double t0, doubl
     return fail(DG_ERR_ARG, "the jump record must be 16-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t field = p->ktot * p->NP;
+  {  // uN == u0 is the one alias
+    const size_t fb = sizeof(double) * size_t(field);
+    if (const int rc = disjoint({{"u0", u0, fb}, {"uN", uN == u0 ? nullptr : uN, fb},
+                                 {"jumps", jumps, sizeof(double) * size_t(nsteps) *
+                                                      size_t(rec_ld(p->ktot))}}))
+      return rc;
+  }
   if (nsteps == 0) {
     if (uN != u0)
       HIP_TRY(hipMemcpyAsync(uN, u0, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
@@ -1746,9 +1776,14 @@ int dg_lserk4_adj_rec(dg_plan* p, double* w, const double* jumps, double t0, dou
   if (reinterpret_cast<uintptr_t>(jumps) % 16 != 0)
     return fail(DG_ERR_ARG, "the jump record must be 16-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t field = p->ktot * p->NP;
+  if (const int rc = disjoint({{"w", w, sizeof(double) * size_t(field)},
+                               {"jumps", jumps, sizeof(double) * size_t(nsteps) *
+                                                    size_t(rec_ld(p->ktot))},
+                               {"eta", eta, sizeof(double) * size_t(p->ktot)}}))
+    return rc;
   if (eta != nullptr && nsteps == 0 && (flags & DG_ADJ_ETA_ASSIGN))
     HIP_TRY(hipMemsetAsync(eta, 0, sizeof(double) * p->ktot, st));
-  const int64_t field = p->ktot * p->NP;
   std::vector<double> tn(size_t(nsteps) + 1), src(size_t(nsteps) + 1, 0.0);
   tn[0] = t0;
   for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
@@ -1792,12 +1827,20 @@ int sweep_rec_impl(dg_plan* p, const double* u0, double* uN, double* w, double* 
     return fail(DG_ERR_ARG, "the jump record is the linear LSERK4 sweep's (use snapshots)");
   if (reinterpret_cast<uintptr_t>(jumps) % 16 != 0)
     return fail(DG_ERR_ARG, "the jump record must be 16-byte aligned");
-  if (uN && (uN == w || uN == u0)) return fail(DG_ERR_ARG, "uN must not alias u0 or w");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool term = (flags & DG_SWEEP_TERMINAL_STATE) != 0;
   const int aflags = flags & (DG_ADJ_ETA_ASSIGN | DG_ADJ_ETA_ABS);
   const int64_t field = p->ktot * p->NP;
   const size_t fbytes = sizeof(double) * size_t(field);
+  // No alias at all: u0 is an input the call leaves untouched, and w == u0 would have the
+  // launch chains run the forward in place on it.
+  if (const int rc = disjoint({{"u0", u0, fbytes}, {"uN", uN, fbytes}, {"w", w, fbytes},
+                               {"jumps", jumps, sizeof(double) * size_t(nsteps) *
+                                                    size_t(rec_ld(p->ktot))},
+                               {"eta", eta, sizeof(double) * size_t(p->ktot)},
+                               {"idx", idx, sizeof(int64_t)}, {"value", value, sizeof(double)},
+                               {"nonfinite_count", nonfinite, sizeof(int64_t)}}))
+    return rc;
   int waves = 0, msf = 0, msa = 0;
   if (!sweep_shape(p, nsteps, &waves, &msf, &msa)) {
     // the launch-per-block pair: forward into uN (or w when it is the terminal weight, or a
@@ -1971,7 +2014,11 @@ int dg_sweep_status(dg_plan* p, int* status, void* stream) {
 
 int dg_slope_limit_n(dg_plan* p, const double* u, double* ulim, int32_t* ids, void* stream) {
   if (!p || !u || !ulim) return fail(DG_ERR_ARG, "null argument");
-  if (u == ulim) return fail(DG_ERR_ARG, "in-place limiting is not supported (tiles overlap)");
+  // (in-place or shifted limiting races: a tile reads its neighbours' elements as a halo)
+  const size_t fb = sizeof(double) * size_t(p->ktot) * size_t(p->NP);
+  if (const int rc = disjoint({{"u", u, fb}, {"ulim", ulim, fb},
+                               {"ids_mask", ids, sizeof(int32_t) * size_t(p->ktot)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(p->ktot, kBlock - 2);
   DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_limit<NP, false>), dim3(grid), dim3(kBlock), 0, st,
@@ -1982,7 +2029,8 @@ int dg_slope_limit_n(dg_plan* p, const double* u, double* ulim, int32_t* ids, vo
 
 int dg_slope_limit_1(dg_plan* p, const double* u, double* ulim, void* stream) {
   if (!p || !u || !ulim) return fail(DG_ERR_ARG, "null argument");
-  if (u == ulim) return fail(DG_ERR_ARG, "in-place limiting is not supported (tiles overlap)");
+  const size_t fb = sizeof(double) * size_t(p->ktot) * size_t(p->NP);
+  if (const int rc = disjoint({{"u", u, fb}, {"ulim", ulim, fb}})) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(p->ktot, kBlock - 2);
   DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_limit<NP, true>), dim3(grid), dim3(kBlock), 0, st,
@@ -1994,6 +2042,8 @@ int dg_slope_limit_1(dg_plan* p, const double* u, double* ulim, void* stream) {
 int dg_argmax(dg_plan* p, const double* x, int64_t n, int use_abs, int64_t* idx, void* stream) {
   if (!p || !x || !idx) return fail(DG_ERR_ARG, "null argument");
   if (n < 1 || n > p->ktot * p->NP) return fail(DG_ERR_ARG, "n out of range");
+  if (const int rc = disjoint({{"x", x, sizeof(double) * size_t(n)}, {"idx", idx, sizeof(int64_t)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int64_t parts = (n + 4 * kBlock - 1) / (4 * kBlock);
   if (parts > kArgmaxParts) parts = kArgmaxParts;
@@ -2010,6 +2060,10 @@ int dg_argmax_ex(dg_plan* p, const double* x, int64_t n, int use_abs, int64_t* i
                  double* value, int64_t* nonfinite_count, void* stream) {
   if (!p || !x || !idx) return fail(DG_ERR_ARG, "null argument");
   if (n < 1 || n > p->ktot * p->NP) return fail(DG_ERR_ARG, "n out of range");
+  if (const int rc = disjoint({{"x", x, sizeof(double) * size_t(n)}, {"idx", idx, sizeof(int64_t)},
+                               {"value", value, sizeof(double)},
+                               {"nonfinite_count", nonfinite_count, sizeof(int64_t)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int64_t parts = (n + 4 * kBlock - 1) / (4 * kBlock);
   if (parts > kArgmaxParts) parts = kArgmaxParts;
@@ -2025,6 +2079,9 @@ int dg_argmax_ex(dg_plan* p, const double* x, int64_t n, int use_abs, int64_t* i
 int dg_sum_rows(const double* x, int64_t rows, int64_t n, double* out, void* stream) {
   if (!x || !out) return fail(DG_ERR_ARG, "null argument");
   if (rows < 1 || n < 1) return fail(DG_ERR_ARG, "rows and n must be >= 1");
+  if (const int rc = disjoint({{"x", x, sizeof(double) * size_t(rows) * size_t(n)},
+                               {"out", out, sizeof(double) * size_t(n)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_sum_rows, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, x, rows, n, out);
   HIP_TRY(hipGetLastError());
@@ -2037,6 +2094,10 @@ int dg_slice_candidate(dg_plan* p, const double* x, int64_t rows, int64_t n, int
   if (rows < 1 || n < 1 || ld < n) return fail(DG_ERR_ARG, "rows, n >= 1 and ld >= n required");
   if (n > p->ktot * p->NP) return fail(DG_ERR_ARG, "n out of range");
   if (!(divisor > 0.0)) return fail(DG_ERR_ARG, "divisor must be positive");
+  // (the last row is read up to column n only)
+  if (const int rc = disjoint({{"x", x, sizeof(double) * (size_t(rows - 1) * size_t(ld) + size_t(n))},
+                               {"cand", cand, 2 * sizeof(int64_t)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int64_t parts = (n + 4 * kBlock - 1) / (4 * kBlock);
   if (parts > kArgmaxParts) parts = kArgmaxParts;
@@ -2053,6 +2114,10 @@ int dg_candidates_argmax(const int64_t* cands, int64_t w, int64_t* idx, double* 
                          int64_t* nonfinite_count, void* stream) {
   if (!cands || !idx) return fail(DG_ERR_ARG, "null argument");
   if (w < 1) return fail(DG_ERR_ARG, "w must be >= 1");
+  if (const int rc = disjoint({{"cands", cands, 2 * sizeof(int64_t) * size_t(w)},
+                               {"idx", idx, sizeof(int64_t)}, {"value", value, sizeof(double)},
+                               {"nonfinite_count", nonfinite_count, sizeof(int64_t)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_candidates, dim3(1), dim3(kBlock), 0, st, cands, w, idx, value,
                      nonfinite_count);
@@ -2063,6 +2128,13 @@ int dg_candidates_argmax(const int64_t* cands, int64_t w, int64_t* idx, double* 
 int dg_init_sine(const dg_plan* p, const double* amp, const double* freq, const double* phase,
                  double* u, void* stream) {
   if (!p || !amp || !freq || !phase || !u) return fail(DG_ERR_ARG, "null argument");
+  {  // the three inputs are only read and may share memory; u may not touch any of them
+    const size_t fb = sizeof(double) * size_t(p->ktot) * size_t(p->NP);
+    const size_t bb = sizeof(double) * size_t(p->batch);
+    for (const ArgRange& in : {ArgRange{"amp", amp, bb}, ArgRange{"freq", freq, bb},
+                               ArgRange{"phase", phase, bb}})
+      if (const int rc = disjoint({in, {"u", u, fb}})) return rc;
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(p->ktot, kBlock);
   DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_init_sine<NP>), dim3(grid), dim3(kBlock), 0, st,

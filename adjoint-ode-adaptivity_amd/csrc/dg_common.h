@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <tuple>
@@ -102,6 +103,34 @@ constexpr size_t kMarkBytes = 16384;
 
 // Sets the calling thread's dg_last_error() text and returns `code` (dg_advec.hip).
 int fail(int code, const std::string& msg);
+
+// The buffer contract of include/dg_advec.h ("Aliasing and alignment").  Host only.
+// True when the half-open byte ranges [x, x + nx) and [y, y + ny) share a byte: two buffers
+// that touch (one's end is the other's start) do not overlap.
+inline bool overlap(const void* x, size_t nx, const void* y, size_t ny) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+  return a < b + ny && b < a + nx;
+}
+
+// One array argument of a compute call: its name in the header and the bytes the call's
+// kernels read or write through it (from the plan's sizes and nsteps).
+struct ArgRange {
+  const char* name;
+  const void* ptr;
+  size_t bytes;
+};
+
+// DG_OK when the ranges are pairwise disjoint, else DG_ERR_ARG naming the first pair that
+// overlaps.  Null pointers and empty ranges are skipped, so an entry point passes nullptr for
+// an absent argument and for the one it documents as an exact alias of (part of) another.
+inline int disjoint(std::initializer_list<ArgRange> args) {
+  for (const ArgRange* i = args.begin(); i != args.end(); ++i)
+    for (const ArgRange* j = i + 1; j != args.end(); ++j)
+      if (i->ptr && j->ptr && i->bytes && j->bytes && overlap(i->ptr, i->bytes, j->ptr, j->bytes))
+        return fail(DG_ERR_ARG, std::string(i->name) + " and " + j->name +
+                                    " overlap (the byte ranges of a call's arrays must be disjoint)");
+  return DG_OK;
+}
 
 #define HIP_TRY(expr)                                                              \
   do {                                                                             \

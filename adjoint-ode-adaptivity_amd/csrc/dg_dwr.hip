@@ -1223,9 +1223,17 @@ int adj_p_impl(dg_plan* lo, dg_plan* hi, const double* P, double* w, const doubl
   if (int rc = check_pair(lo, hi)) return rc;
   if (lo->NP > 8) return fail(DG_ERR_ARG, "the p-estimate supports N <= 7");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t field_lo = lo->ktot * lo->NP, field_hi = hi->ktot * hi->NP;
+  // no alias: w is an order-(N+1) field, so it is no snapshot row
+  if (const int rc = disjoint({{"w", w, sizeof(double) * size_t(field_hi)},
+                               {"snapshots", snapshots,
+                                sizeof(double) * size_t(field_lo) * (size_t(nsteps) + 1)},
+                               {"eta", eta, sizeof(double) * size_t(lo->ktot)},
+                               {"idx", idx, sizeof(int64_t)}, {"value", value, sizeof(double)},
+                               {"nonfinite_count", nonfinite, sizeof(int64_t)}}))
+    return rc;
   if (eta != nullptr && nsteps == 0 && (flags & DG_ADJ_ETA_ASSIGN))
     HIP_TRY(hipMemsetAsync(eta, 0, sizeof(double) * lo->ktot, st));
-  const int64_t field_lo = lo->ktot * lo->NP, field_hi = hi->ktot * hi->NP;
   if (term && (nsteps == 0 || p_horner() == 0)) {
     // the round-3 kernel (and an empty sweep) take the terminal weight from w: form it first
     if (const int rc = dg_prolong(lo, hi, P, snapshots + int64_t(nsteps) * field_lo, w, stream))
@@ -1289,6 +1297,9 @@ int dg_prolong(const dg_plan* lo, const dg_plan* hi, const double* P, const doub
   if (!lo || !hi || !P || !u || !u_hi) return fail(DG_ERR_ARG, "null argument");
   if (hi->NP != lo->NP + 1 || hi->ktot != lo->ktot)
     return fail(DG_ERR_ARG, "the enriched plan must have order N+1 and the same elements");
+  if (const int rc = disjoint({{"u", u, sizeof(double) * size_t(lo->ktot) * size_t(lo->NP)},
+                               {"u_hi", u_hi, sizeof(double) * size_t(hi->ktot) * size_t(hi->NP)}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int rc = DG_OK;
   switch (lo->NP) {
@@ -1365,6 +1376,14 @@ int dg_lserk4_sweep_p(dg_plan* lo, dg_plan* hi, const double* P, double* snapsho
     return fail(DG_ERR_ARG, "unknown flags (the terminal weight is always P u^nsteps)");
   if (int rc = check_pair(lo, hi)) return rc;
   if (lo->NP > 8) return fail(DG_ERR_ARG, "the p-estimate supports N <= 7");
+  if (const int rc = disjoint(
+          {{"snapshots", snapshots,
+            sizeof(double) * size_t(lo->ktot) * size_t(lo->NP) * (size_t(nsteps) + 1)},
+           {"w", w, sizeof(double) * size_t(hi->ktot) * size_t(hi->NP)},
+           {"eta", eta, sizeof(double) * size_t(lo->ktot)}, {"idx", idx, sizeof(int64_t)},
+           {"value", value, sizeof(double)},
+           {"nonfinite_count", nonfinite_count, sizeof(int64_t)}}))
+    return rc;
   if (!p_sweep_shape(lo, nsteps)) {
     // the launch chains: the snapshot forward in place from snapshot 0 -- on the stage-loop
     // workgroup tiles at 4 steps per launch, the dataflow launch's forward blocks, so that the

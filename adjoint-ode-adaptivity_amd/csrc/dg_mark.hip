@@ -442,6 +442,9 @@ extern "C" int dg_plan_mark(dg_plan* p, const double* eta, int strategy, double 
                             int64_t max_marked, uint8_t* marks, int64_t* info, void* stream) {
   if (!p || !eta || !marks || !info) return fail(DG_ERR_ARG, "null argument");
   const int64_t K = p->K;
+  if (const int rc = disjoint({{"eta", eta, sizeof(double) * size_t(K)},
+                               {"marks", marks, size_t(K)}, {"info", info, 4 * sizeof(int64_t)}}))
+    return rc;
   const int64_t cap = (max_marked < 0 || max_marked > K) ? K : max_marked;
   int mode = 0;       // k_mark_end: 0 nothing, 1 the select's set, 2 every candidate
   int64_t m = 0;      // ranks the select places
@@ -499,6 +502,12 @@ extern "C" int dg_plan_refine_marked(dg_plan* p, const uint8_t* marks, int32_t* 
   MarkState* ms = static_cast<MarkState*>(p->d_mark);
   int* sums = reinterpret_cast<int*>(p->d_scratch2);
   const int64_t K = p->K;
+  // parent holds K + splits entries: at least K, checked before anything is enqueued, and its
+  // true extent again below once the scan has counted the splits (before parent or the mesh is
+  // written; the scan only reads marks and writes plan scratch)
+  if (const int rc = disjoint({{"marks", marks, size_t(K)},
+                               {"parent", parent, sizeof(int32_t) * size_t(K)}}))
+    return rc;
   const unsigned grid = grid_for(K, kMarkElems);
   hipLaunchKernelGGL(k_marks_sum, dim3(grid), dim3(kBlock), 0, st, marks, K, sums);
   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, st, sums, int64_t(grid), &ms->total);
@@ -510,6 +519,9 @@ extern "C" int dg_plan_refine_marked(dg_plan* p, const uint8_t* marks, int32_t* 
   if (K + total > p->K_cap)
     return fail(DG_ERR_ARG, "marked splits exceed the plan's capacity: call dg_plan_reserve "
                             "first, or mark with max_marked = capacity - K");
+  if (const int rc = disjoint({{"marks", marks, size_t(K)},
+                               {"parent", parent, sizeof(int32_t) * size_t(K + total)}}))
+    return rc;
   if (total == 0) {
     // nothing to split: the mesh (and `uniform`) stay as they are; parent is the identity
     if (parent != nullptr) {

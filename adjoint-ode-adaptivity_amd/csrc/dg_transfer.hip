@@ -240,11 +240,6 @@ __global__ __launch_bounds__(kBlock) void k_from_children(const double* __restri
                   a.vec_out != 0);
 }
 
-bool overlap(const void* x, size_t nx, const void* y, size_t ny) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
-  return a < b + ny && b < a + nx;
-}
-
 template <bool TO>
 int transfer(const dg_plan* p, const int32_t* parent, int64_t k_old, const double* A,
              const double* in, double* out, void* stream) {
@@ -255,8 +250,9 @@ int transfer(const dg_plan* p, const int32_t* parent, int64_t k_old, const doubl
                             "midpoint splits)");
   const size_t n_old = size_t(p->batch) * size_t(k_old) * size_t(p->NP) * sizeof(double);
   const size_t n_new = size_t(p->ktot) * size_t(p->NP) * sizeof(double);
-  if (overlap(in, TO ? n_old : n_new, out, TO ? n_new : n_old))
-    return fail(DG_ERR_ARG, "the input and output fields overlap");
+  if (const int rc = disjoint({{"parent", parent, sizeof(int32_t) * size_t(K)},
+                               {"in", in, TO ? n_old : n_new}, {"out", out, TO ? n_new : n_old}}))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   DG_DISPATCH_NP(p->NP, {
     TransferArgs<NP> a;

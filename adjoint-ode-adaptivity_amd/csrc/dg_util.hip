@@ -36,6 +36,9 @@ extern "C" int dg_stream_copy(const double* src, double* dst, int64_t n, void* s
   if (n < 0) return fail(DG_ERR_ARG, "n < 0");
   if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15)
     return fail(DG_ERR_ARG, "src and dst must be 16-byte aligned");
+  if (const int rc = disjoint({{"src", src, sizeof(double) * size_t(n)},
+                               {"dst", dst, sizeof(double) * size_t(n)}}))
+    return rc;
   if (n == 0) return DG_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n2 = n / 2;

@@ -48,6 +48,30 @@ def _stream(device):
   return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _cuda(t, dtype, name, numel=1, device=None):
+  """The device pointer of ``t``, a contiguous CUDA tensor of ``dtype`` with at least ``numel``
+  elements (on ``device`` if given): what a kernel that writes ``numel`` elements needs."""
+  if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype
+      or not t.is_contiguous()):
+    raise TypeError(f"{name} must be a contiguous CUDA {dtype} tensor (no CPU path)")
+  if device is not None and t.device != device:
+    raise TypeError(f"{name} is on {t.device}, expected {device}")
+  if t.numel() < numel:
+    raise ValueError(f"{name} has {t.numel()} elements, need {numel}")
+  return ctypes.c_void_p(t.data_ptr())
+
+
+def _out1(t, dtype, name, device=None):
+  """A nullable one-element result of the refine decision (``idx`` / ``value`` /
+  ``nonfinite``): None, a device address (``host_alias`` of pinned host memory) or a CUDA
+  tensor of ``dtype`` with at least one element."""
+  if t is None:
+    return None
+  if isinstance(t, int):
+    return ctypes.c_void_p(t)
+  return _cuda(t, dtype, name, 1, device)
+
+
 class DGAdvection1D:
   """A plan for ``batch`` trajectories of 1D linear advection on one nodal-DG mesh.
 
@@ -218,14 +242,9 @@ class DGAdvection1D:
     MAIN.m:137-141).  K grows by one; fields of the old size are re-initialised or carried
     over with ``transfer(u, parent_of_split(idx, k_old), k_old)``.
     ``h_split`` (1-element CUDA float64, optional) receives the split element's width."""
-    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int64:
-      raise TypeError("idx must be a CUDA int64 tensor")
-    hp = None
-    if h_split is not None:
-      if not h_split.is_cuda or h_split.dtype != torch.float64:
-        raise TypeError("h_split must be a CUDA float64 tensor")
-      hp = ctypes.c_void_p(h_split.data_ptr())
-    rc = self._lib.dg_plan_refine(self._plan, ctypes.c_void_p(idx.data_ptr()), hp,
+    ip = _cuda(idx, torch.int64, "idx", 1, self.device)
+    hp = None if h_split is None else _cuda(h_split, torch.float64, "h_split", 1, self.device)
+    rc = self._lib.dg_plan_refine(self._plan, ip, hp,
                                   _stream(self.device))
     _lib.check(rc, "dg_plan_refine")
     self._query()
@@ -268,8 +287,9 @@ class DGAdvection1D:
     pp = None
     if parent is not None:
       if (not isinstance(parent, torch.Tensor) or not parent.is_cuda
-          or parent.dtype != torch.int32 or not parent.is_contiguous()):
-        raise TypeError("parent must be a contiguous CUDA int32 tensor")
+          or parent.dtype != torch.int32 or not parent.is_contiguous()
+          or parent.device != self.device):
+        raise TypeError(f"parent must be a contiguous CUDA int32 tensor on {self.device}")
       n_marked = int(torch.count_nonzero(marks).item())
       if parent.numel() < self.K + n_marked:
         raise ValueError(f"parent has {parent.numel()} elements, the refined mesh "
@@ -329,8 +349,9 @@ class DGAdvection1D:
 
   def _parent(self, parent):
     if (not isinstance(parent, torch.Tensor) or not parent.is_cuda
-        or parent.dtype != torch.int32 or not parent.is_contiguous()):
-      raise TypeError("parent must be a contiguous CUDA int32 tensor")
+        or parent.dtype != torch.int32 or not parent.is_contiguous()
+        or parent.device != self.device):
+      raise TypeError(f"parent must be a contiguous CUDA int32 tensor on {self.device}")
     if parent.numel() != self.K:
       raise ValueError(f"parent has {parent.numel()} elements, the refined mesh {self.K}")
     return ctypes.c_void_p(parent.data_ptr())
@@ -383,6 +404,8 @@ class DGAdvection1D:
       raise TypeError(f"{name} must be a CUDA tensor (no CPU path)")
     if t.dtype != dtype:
       raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.device != self.device:
+      raise TypeError(f"{name} is on {t.device}, the plan on {self.device}")
     if not t.is_contiguous():
       raise ValueError(f"{name} must be contiguous")
     want = self.field_numel if numel is None else numel
@@ -406,12 +429,8 @@ class DGAdvection1D:
   def _decisions(self, decisions, nsteps):
     if decisions is None:
       return None
-    if (not isinstance(decisions, torch.Tensor) or not decisions.is_cuda
-        or decisions.dtype != torch.int16 or not decisions.is_contiguous()):
-      raise TypeError("decisions must be a contiguous CUDA int16 tensor (uint16 bits)")
-    if decisions.numel() < nsteps * self.ktot:
-      raise ValueError(f"decisions holds {decisions.numel()} words, need {nsteps * self.ktot}")
-    return ctypes.c_void_p(decisions.data_ptr())
+    return _cuda(decisions, torch.int16, "decisions (uint16 bits)", nsteps * self.ktot,
+                 self.device)
 
   def forward(self, u, t0, dt, nsteps, snapshots=None, decisions=None):
     """nsteps fused steps in place on u (One_code.mlx:119-140); optional snapshots
@@ -509,14 +528,6 @@ class DGAdvection1D:
     (dg_lserk4_sweep_refine): in the dataflow launch the last adjoint tiles reduce the argmax
     themselves.  ``idx`` / ``nonfinite`` (CUDA int64, 1) and ``value`` (CUDA float64, 1) as
     for ``argmax_ex``."""
-    def p1(t, dtype, name):
-      if t is None:
-        return None
-      if isinstance(t, int):  # a device address (host_alias of pinned host memory)
-        return ctypes.c_void_p(t)
-      if not t.is_cuda or t.dtype != dtype or t.numel() < 1:
-        raise TypeError(f"{name} must be a CUDA {dtype} tensor or a device address")
-      return ctypes.c_void_p(t.data_ptr())
     flags = ((_lib.DG_ADJ_ETA_ASSIGN if eta_assign else 0) |
              (_lib.DG_ADJ_ETA_ABS if eta_abs else 0) |
              (_lib.DG_SWEEP_TERMINAL_STATE if terminal_state else 0))
@@ -524,8 +535,9 @@ class DGAdvection1D:
     rc = self._lib.dg_lserk4_sweep_refine(
         self._plan, self._field(u0, "u0"), un_p, self._field(w, "w"), self._jumps(jumps, nsteps),
         float(t0), float(dt), int(nsteps), self._field(eta, "eta", self.ktot), int(flags),
-        p1(idx, torch.int64, "idx"), p1(value, torch.float64, "value"),
-        p1(nonfinite, torch.int64, "nonfinite"), _stream(self.device))
+        _out1(idx, torch.int64, "idx", self.device),
+        _out1(value, torch.float64, "value", self.device),
+        _out1(nonfinite, torch.int64, "nonfinite", self.device), _stream(self.device))
     _lib.check(rc, "dg_lserk4_sweep_refine")
     return idx
 
@@ -563,9 +575,7 @@ class DGAdvection1D:
     item: size it with ``DWREstimate.trace_words``); None turns it off."""
     ptr = None
     if trace is not None:
-      if not trace.is_cuda or trace.dtype != torch.int64 or not trace.is_contiguous():
-        raise TypeError("trace must be a contiguous CUDA int64 tensor")
-      ptr = ctypes.c_void_p(trace.data_ptr())
+      ptr = _cuda(trace, torch.int64, "trace", 0, self.device)
     _lib.check(self._lib.dg_plan_sweep_trace(self._plan, ptr), "dg_plan_sweep_trace")
     self._trace = trace
 
@@ -604,11 +614,10 @@ class DGAdvection1D:
   def argmax_async(self, x, use_abs=True, out=None):
     """Device-side argmax (numpy semantics) into a 1-element int64 tensor."""
     out = self._idx if out is None else out
-    n = x.numel()
-    if not x.is_cuda or x.dtype != torch.float64 or not x.is_contiguous():
-      raise TypeError("x must be a contiguous CUDA float64 tensor")
-    rc = self._lib.dg_argmax(self._plan, ctypes.c_void_p(x.data_ptr()), n, int(use_abs),
-                             ctypes.c_void_p(out.data_ptr()), _stream(self.device))
+    xp = _cuda(x, torch.float64, "x", 1, self.device)
+    rc = self._lib.dg_argmax(self._plan, xp, x.numel(), int(use_abs),
+                             _cuda(out, torch.int64, "out", 1, self.device),
+                             _stream(self.device))
     _lib.check(rc, "dg_argmax")
     return out
 
@@ -619,16 +628,12 @@ class DGAdvection1D:
     """argmax into ``idx`` (1-element CUDA int64) plus, on the device, the winning value into
     ``value`` (1-element CUDA float64) and +1 into ``nonfinite`` (1-element CUDA int64) when
     that value is not finite (dg_argmax_ex; no host sync)."""
-    n = x.numel()
-    if not x.is_cuda or x.dtype != torch.float64 or not x.is_contiguous():
-      raise TypeError("x must be a contiguous CUDA float64 tensor")
-    for t, name, dt_ in ((idx, "idx", torch.int64), (value, "value", torch.float64),
-                         (nonfinite, "nonfinite", torch.int64)):
-      if t is not None and (not t.is_cuda or t.dtype != dt_ or t.numel() < 1):
-        raise TypeError(f"{name} must be a CUDA {dt_} tensor")
-    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    rc = self._lib.dg_argmax_ex(self._plan, ctypes.c_void_p(x.data_ptr()), n, int(use_abs),
-                                ptr(idx), ptr(value), ptr(nonfinite), _stream(self.device))
+    xp = _cuda(x, torch.float64, "x", 1, self.device)
+    rc = self._lib.dg_argmax_ex(self._plan, xp, x.numel(), int(use_abs),
+                                _cuda(idx, torch.int64, "idx", 1, self.device),
+                                _out1(value, torch.float64, "value", self.device),
+                                _out1(nonfinite, torch.int64, "nonfinite", self.device),
+                                _stream(self.device))
     _lib.check(rc, "dg_argmax_ex")
     return idx
 
@@ -636,14 +641,15 @@ class DGAdvection1D:
     """This rank's refine candidate from its received slices x (rows, ld) CUDA float64:
     cand (CUDA int64[2]) = (bits of |m[i]|, i + offset), m = the rows' ascending sum over the
     first n columns / divisor, i = argmax |m| (dg_slice_candidate; no host sync)."""
-    if not x.is_cuda or x.dtype != torch.float64 or x.dim() != 2 or not x.is_contiguous():
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
       raise TypeError("x must be a contiguous 2-D CUDA float64 tensor")
-    if not cand.is_cuda or cand.dtype != torch.int64 or cand.numel() < 2:
-      raise TypeError("cand must be a CUDA int64 tensor of 2 elements")
+    xp = _cuda(x, torch.float64, "x", 1, self.device)
+    cp = _cuda(cand, torch.int64, "cand", 2, self.device)
     rows, ld = x.shape
-    rc = self._lib.dg_slice_candidate(self._plan, ctypes.c_void_p(x.data_ptr()), int(rows),
-                                      int(n), int(ld), float(divisor), int(offset),
-                                      ctypes.c_void_p(cand.data_ptr()), _stream(self.device))
+    if not 1 <= int(n) <= ld:
+      raise ValueError(f"n = {n} columns of rows that are {ld} long")
+    rc = self._lib.dg_slice_candidate(self._plan, xp, int(rows), int(n), int(ld),
+                                      float(divisor), int(offset), cp, _stream(self.device))
     _lib.check(rc, "dg_slice_candidate")
     return cand
 
@@ -743,14 +749,6 @@ class DWREstimate:
     ``w`` (order N+1, swept back to t_0) and ``eta``; with ``idx`` also the refine decision
     (as ``estimate_refine``).  One dataflow launch where ``query_sweep`` says so, else the
     launch chains; bit-identical to ``lo.forward`` at 4 steps per launch + ``estimate``."""
-    def p1(t, dtype, name):
-      if t is None:
-        return None
-      if isinstance(t, int):  # a device address (host_alias of pinned host memory)
-        return ctypes.c_void_p(t)
-      if not t.is_cuda or t.dtype != dtype or t.numel() < 1:
-        raise TypeError(f"{name} must be a CUDA {dtype} tensor or a device address")
-      return ctypes.c_void_p(t.data_ptr())
     eta_p = None if eta is None else self.lo._field(eta, "eta", self.lo.ktot)
     flags = ((_lib.DG_ADJ_ETA_ASSIGN if eta_assign else 0) |
              (_lib.DG_ADJ_ETA_ABS if eta_abs else 0))
@@ -758,8 +756,9 @@ class DWREstimate:
         self.lo._plan, self.hi._plan, self._P_ptr,
         self.lo._field(snapshots, "snapshots", (nsteps + 1) * self.lo.field_numel),
         self.hi._field(w, "w"), float(t0), float(dt), int(nsteps), eta_p, int(flags),
-        p1(idx, torch.int64, "idx"), p1(value, torch.float64, "value"),
-        p1(nonfinite, torch.int64, "nonfinite"), _stream(self.lo.device))
+        _out1(idx, torch.int64, "idx", self.lo.device),
+        _out1(value, torch.float64, "value", self.lo.device),
+        _out1(nonfinite, torch.int64, "nonfinite", self.lo.device), _stream(self.lo.device))
     _lib.check(rc, "dg_lserk4_sweep_p")
     return w, eta
 
@@ -801,14 +800,6 @@ class DWREstimate:
     (dg_lserk4_adj_p_refine): in the dataflow launch the last block's tiles reduce the argmax
     themselves.  ``idx`` / ``nonfinite`` (CUDA int64, 1) and ``value`` (CUDA float64, 1) as
     for ``argmax_ex``."""
-    def p1(t, dtype, name):
-      if t is None:
-        return None
-      if isinstance(t, int):  # a device address (host_alias of pinned host memory)
-        return ctypes.c_void_p(t)
-      if not t.is_cuda or t.dtype != dtype or t.numel() < 1:
-        raise TypeError(f"{name} must be a CUDA {dtype} tensor or a device address")
-      return ctypes.c_void_p(t.data_ptr())
     flags = ((_lib.DG_ADJ_ETA_ASSIGN if eta_assign else 0) |
              (_lib.DG_ADJ_ETA_ABS if eta_abs else 0) |
              (_lib.DG_ADJ_P_TERMINAL_PROLONG if terminal_prolong else 0))
@@ -816,8 +807,9 @@ class DWREstimate:
         self.lo._plan, self.hi._plan, self._P_ptr, self.hi._field(w, "w"),
         self.lo._field(snapshots, "snapshots", (nsteps + 1) * self.lo.field_numel),
         float(t0), float(dt), int(nsteps), self.lo._field(eta, "eta", self.lo.ktot), int(flags),
-        p1(idx, torch.int64, "idx"), p1(value, torch.float64, "value"),
-        p1(nonfinite, torch.int64, "nonfinite"), _stream(self.lo.device))
+        _out1(idx, torch.int64, "idx", self.lo.device),
+        _out1(value, torch.float64, "value", self.lo.device),
+        _out1(nonfinite, torch.int64, "nonfinite", self.lo.device), _stream(self.lo.device))
     _lib.check(rc, "dg_lserk4_adj_p_refine")
     return idx
 
@@ -841,13 +833,11 @@ def stream_copy(src, dst):
   """dst = src with the library's 16-byte-per-lane copy kernel (dg_stream_copy): the
   achievable-HBM-bandwidth ceiling the bench reports."""
   lib = _lib.load()
-  for t in (src, dst):
-    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
-      raise TypeError("stream_copy needs contiguous CUDA float64 tensors")
+  sp = _cuda(src, torch.float64, "src", 0)
+  dp = _cuda(dst, torch.float64, "dst", 0, src.device)
   if src.numel() != dst.numel():
     raise ValueError("src and dst differ in size")
-  rc = lib.dg_stream_copy(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-                          src.numel(), _stream(src.device))
+  rc = lib.dg_stream_copy(sp, dp, src.numel(), _stream(src.device))
   _lib.check(rc, "dg_stream_copy")
   return dst
 
@@ -855,12 +845,14 @@ def stream_copy(src, dst):
 def sum_rows(x, rows, out=None):
   """out[k] = sum_r x[r, k] in ascending r (dg_sum_rows)."""
   lib = _lib.load()
-  if not x.is_cuda or x.dtype != torch.float64 or not x.is_contiguous():
-    raise TypeError("x must be a contiguous CUDA float64 tensor")
+  xp = _cuda(x, torch.float64, "x", 1)
+  rows = int(rows)
+  if rows < 1 or x.numel() % rows != 0:
+    raise ValueError(f"x has {x.numel()} elements: not {rows} rows of equal length")
   n = x.numel() // rows
   out = torch.empty(n, dtype=torch.float64, device=x.device) if out is None else out
-  rc = lib.dg_sum_rows(ctypes.c_void_p(x.data_ptr()), int(rows), int(n),
-                       ctypes.c_void_p(out.data_ptr()), _stream(x.device))
+  rc = lib.dg_sum_rows(xp, rows, int(n), _cuda(out, torch.float64, "out", n, x.device),
+                       _stream(x.device))
   _lib.check(rc, "dg_sum_rows")
   return out
 
@@ -869,10 +861,12 @@ def candidates_argmax(cands, idx, value=None, nonfinite=None):
   """The refine decision from the ranks' candidates (CUDA int64 (W, 2), rank order) into idx
   (and value / +1 nonfinite) on the device (dg_candidates_argmax)."""
   lib = _lib.load()
-  if not cands.is_cuda or cands.dtype != torch.int64 or not cands.is_contiguous():
-    raise TypeError("cands must be a contiguous CUDA int64 tensor")
-  ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-  rc = lib.dg_candidates_argmax(ctypes.c_void_p(cands.data_ptr()), cands.numel() // 2, ptr(idx),
-                                ptr(value), ptr(nonfinite), _stream(cands.device))
+  cp = _cuda(cands, torch.int64, "cands", 2)
+  if cands.numel() % 2 != 0:
+    raise ValueError(f"cands has {cands.numel()} elements: not (value bits, index) pairs")
+  dev = cands.device
+  rc = lib.dg_candidates_argmax(cp, cands.numel() // 2, _cuda(idx, torch.int64, "idx", 1, dev),
+                                _out1(value, torch.float64, "value", dev),
+                                _out1(nonfinite, torch.int64, "nonfinite", dev), _stream(dev))
   _lib.check(rc, "dg_candidates_argmax")
   return idx

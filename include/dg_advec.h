@@ -20,6 +20,19 @@
  *    the caller synchronises.  A plan may be shared by threads that use different streams
  *    for dg_advec_rhs / dg_slope_limit_n; dg_lserk4_fwd / dg_lserk4_adj / dg_argmax use
  *    plan scratch and must not run concurrently on one plan.
+ *  - Aliasing and alignment: the byte ranges of any two array arguments of one compute call
+ *    must be disjoint, unless that entry point's comment has an "Alias:" line that says
+ *    otherwise.  A range is [pointer, pointer + bytes) with the bytes the call reads or writes
+ *    through that argument, from the plan's sizes and nsteps (a field is batch*K*Np doubles,
+ *    snapshots (nsteps+1) fields, the jump record nsteps*LD doubles, decisions nsteps*batch*K
+ *    uint16, eta batch*K doubles, idx / value / nonfinite_count 8 bytes each).  Ranges are
+ *    half-open: buffers that touch (one ends where the other starts) are disjoint, so rows of
+ *    one allocation are fine.  An allowed alias is an exact identity of pointers, never a
+ *    partial overlap.  A violation returns DG_ERR_ARG before anything is enqueued on the
+ *    stream (also before the zero fill of an empty sweep's eta).  Null (absent) arguments
+ *    take no part.  Every array needs only its element type's alignment (8 bytes for
+ *    doubles), except where a comment asks for 16 bytes (the jump record, dg_stream_copy);
+ *    those return DG_ERR_ARG otherwise.
  */
 #ifndef DG_ADVEC_H
 #define DG_ADVEC_H
@@ -263,7 +276,12 @@ int dg_plan_mark(dg_plan* plan, const double* eta, int strategy, double param,
  * their total back to the host before it touches the mesh, so it is not capturable in a HIP
  * graph.  K + total > capacity (dg_plan_reserve): DG_ERR_ARG with the mesh untouched.  Otherwise
  * K grows by the total and the mesh is non-uniform from then on, as after dg_plan_refine; with
- * no marks the plan is unchanged (a uniform plan stays uniform). */
+ * no marks the plan is unchanged (a uniform plan stays uniform).
+ * Alias: none, but parent's range is K + splits entries, known only once the marks are
+ * counted: marks inside its first K entries is refused before anything is enqueued, marks
+ * inside the rest after the count (which has read marks and written plan scratch only),
+ * before parent or the mesh is written.  n_split is a host pointer the call writes itself
+ * after its synchronisation, so it has no device range and takes no part. */
 int dg_plan_refine_marked(dg_plan* plan, const uint8_t* marks, int32_t* parent, int64_t* n_split,
                           void* stream);
 
@@ -297,7 +315,7 @@ int dg_plan_query_mark(const dg_plan* plan, int64_t out[4]);
  * Fields are batch * k_old * Np (old) and batch * K * Np (new) doubles in the device layout.
  * Elements whose parent lies outside [0, k_old) are neither read nor written.  No atomics: equal
  * inputs give equal bits.  Asynchronous on stream; no plan scratch is used.  DG_ERR_ARG: a null
- * pointer; k_old < 1, k_old > K or K > 2 k_old; input and output ranges that overlap. */
+ * pointer; k_old < 1, k_old > K or K > 2 k_old; input, output and parent ranges that overlap. */
 int dg_field_to_children(const dg_plan* plan, const int32_t* parent, int64_t k_old,
                          const double* A, const double* in_old, double* out_new, void* stream);
 int dg_field_from_children(const dg_plan* plan, const int32_t* parent, int64_t k_old,
@@ -314,7 +332,8 @@ int dg_advec_rhs(const dg_plan* plan, const double* u, double* rhs, double t, vo
  * (the "dg_march" role; LSERK4 loop One_code.mlx:106-140, time = time + dt as there).
  * u (in/out): the state.  snapshots (nullable): (nsteps+1) consecutive states,
  * snapshots[n] = u^n.  u may alias snapshots[0]: then u^0 is neither copied nor
- * overwritten (u keeps u^0) and the final state is snapshots[nsteps]. */
+ * overwritten (u keeps u^0) and the final state is snapshots[nsteps].
+ * Alias: u == snapshots + 0 exactly; u anywhere else inside snapshots is DG_ERR_ARG. */
 int dg_lserk4_fwd(dg_plan* plan, double* u, double t0, double dt, int nsteps,
                   double* snapshots, void* stream);
 
@@ -322,7 +341,9 @@ int dg_lserk4_fwd(dg_plan* plan, double* u, double t0, double dt, int nsteps,
  * limiter only; ignored otherwise): decisions (nullable, device, nsteps*batch*K uint16) gets,
  * for step n and element e, decisions[n*batch*K + e] = sum over stages s of
  * code_s << (3 s), code_s = 0 (not troubled, SlopeLimitN.m:23) or 4 | (active minmod
- * argument 0..3, minmod.m:9-11).  dg_lserk4_adj_ex reads the record back. */
+ * argument 0..3, minmod.m:9-11).  dg_lserk4_adj_ex reads the record back.
+ * Alias: u == snapshots + 0 exactly, as dg_lserk4_fwd; decisions overlaps neither (its range
+ * counts on plans with a per-stage limiter only, where it is written). */
 int dg_lserk4_fwd_ex(dg_plan* plan, double* u, double t0, double dt, int nsteps,
                      double* snapshots, uint16_t* decisions, void* stream);
 
@@ -338,7 +359,9 @@ int dg_lserk4_fwd_ex(dg_plan* plan, double* u, double t0, double dt, int nsteps,
  *               snapshot (snapshots + nsteps*field, i.e. J = |u^N|^2/2); that snapshot is
  *               then overwritten.
  *   snapshots : the (nsteps+1) forward states written by dg_lserk4_fwd.
- *   eta (nullable): batch*K accumulators (caller zeroes them). */
+ *   eta (nullable): batch*K accumulators (caller zeroes them).
+ * Alias: w == snapshots + nsteps*field exactly (the terminal snapshot); w on any other
+ * snapshot or across two, and eta inside w or snapshots, are DG_ERR_ARG. */
 int dg_lserk4_adj(dg_plan* plan, double* w, const double* snapshots, double t0, double dt,
                   int nsteps, double src_coef, double* eta, void* stream);
 
@@ -357,6 +380,8 @@ enum { DG_ADJ_ETA_ASSIGN = 1, DG_ADJ_ETA_ABS = 2 };
  * nodes), formed in the first launch from the snapshot it reads anyway; w's input is not read
  * (the result equals dg_prolong into w first, bit for bit). */
 enum { DG_ADJ_P_TERMINAL_PROLONG = 8 };
+/* Alias: w == snapshots + nsteps*field exactly, as dg_lserk4_adj; eta and decisions overlap
+ * nothing (decisions counts on plans with a per-stage limiter only). */
 int dg_lserk4_adj_ex(dg_plan* plan, double* w, const double* snapshots, double t0, double dt,
                      int nsteps, double src_coef, double* eta, int flags,
                      const uint16_t* decisions, void* stream);
@@ -378,7 +403,9 @@ int dg_lserk4_adj_ex(dg_plan* plan, double* w, const double* snapshots, double t
  *   an odd batch*K is not written.
  * dg_lserk4_adj_rec: dg_lserk4_adj_ex(w, snapshots, src_coef = 0, eta, flags) with the
  *   record of the same sweep in place of the snapshots (required whenever nsteps > 0, also
- *   without eta: DG_ERR_ARG otherwise). */
+ *   without eta: DG_ERR_ARG otherwise).
+ * Alias (dg_lserk4_fwd_rec): uN == u0 exactly (the sweep in place; no launch writes its own
+ * input).  jumps overlaps neither.  dg_lserk4_adj_rec has no alias. */
 int dg_lserk4_fwd_rec(dg_plan* plan, const double* u0, double* uN, double t0, double dt,
                       int nsteps, double* jumps, void* stream);
 int dg_lserk4_adj_rec(dg_plan* plan, double* w, const double* jumps, double t0, double dt,
@@ -391,7 +418,10 @@ int dg_lserk4_adj_rec(dg_plan* plan, double* w, const double* jumps, double t0, 
  * directions run as ONE dataflow launch: the tiles of every block of steps are work items of a
  * persistent kernel that start as soon as the tiles they read have finished, so the sweep pays
  * one fill and one drain instead of one per launch.  Results are bit-identical to the two calls.
- *   u0 (in): u^0.  uN (nullable, must not alias u0 or w): receives u^nsteps.
+ *   u0 (in): u^0, left untouched.  uN (nullable): receives u^nsteps.  No two of u0, uN, w,
+ *     jumps, eta (and idx / value / nonfinite_count) may overlap; w == u0 in particular is
+ *     DG_ERR_ARG: u0 is an input, and the launch chains would run the forward in place on
+ *     it (the dataflow launch's ordering of w^0's stores against u^0's reads is not relied on).
  *   w (in/out): the terminal weight dJ/du^N on entry -- or, with DG_SWEEP_TERMINAL_STATE,
  *     u^N itself (J = |u^N|^2/2; w's content is ignored) -- and w^0 on exit.
  *   jumps: the record (layout of dg_lserk4_fwd_rec), written and read by the call.
@@ -548,7 +578,8 @@ int dg_argmax(dg_plan* plan, const double* x, int64_t n, int use_abs, int64_t* i
 int dg_argmax_ex(dg_plan* plan, const double* x, int64_t n, int use_abs, int64_t* idx,
                  double* value, int64_t* nonfinite_count, void* stream);
 
-/* dst[0:n] = src[0:n] with 16-byte device loads and stores (both 16-byte aligned): the
+/* dst[0:n] = src[0:n] with 16-byte device loads and stores (both 16-byte aligned, else
+ * DG_ERR_ARG; the ranges must not overlap): the
  * achievable-HBM-bandwidth ceiling of SURVEY 8(d) ("measured with a stream-copy kernel"). */
 int dg_stream_copy(const double* src, double* dst, int64_t n, void* stream);
 
@@ -579,7 +610,9 @@ int dg_candidates_argmax(const int64_t* cands, int64_t w, int64_t* idx, double* 
                          int64_t* nonfinite_count, void* stream);
 
 /* Synthetic ensemble initial conditions u_b(x) = amp[b] * sin(2*pi*freq[b]*x + phase[b])
- * on the plan's mesh (amp/freq/phase: device arrays of length batch). */
+ * on the plan's mesh (amp/freq/phase: device arrays of length batch).
+ * Alias: amp, freq and phase are only read and may be one array or overlap; u overlaps
+ * none of them. */
 int dg_init_sine(const dg_plan* plan, const double* amp, const double* freq,
                  const double* phase, double* u, void* stream);
 
@@ -595,7 +628,9 @@ int dg_init_sine(const dg_plan* plan, const double* amp, const double* freq,
 /* Forward march, order Np-1, Newton per slab until ||U_old - U_next|| <= tol or maxit
  * (dg_march.m:44-68).  S = (V V')\Dr [Np][Np]; Phi [nq][Np] nodal basis at the nq Gauss
  * points (fem_setup.m:30-38); wq [nq] Gauss weights.  Y[(k*Np + i)*n_ics + ic] receives the
- * nodal values of slab k; iters (nullable) [k*n_ics + ic] the Newton iteration counts. */
+ * nodal values of slab k; iters (nullable) [k*n_ics + ic] the Newton iteration counts.
+ * Alias: not checked by the library; the inputs may overlap one another, Y and iters must
+ * overlap nothing (the caller's duty). */
 int dg_time_march(int Np, int nq, const double* S, const double* Phi, const double* wq,
                   int n_slabs, const double* times, int64_t n_ics, const double* y0, double tol,
                   int maxit, double* Y, int32_t* iters, void* stream);
@@ -606,7 +641,9 @@ int dg_time_march(int Np, int nq, const double* S, const double* Phi, const doub
  * and Ma = inv(V V') [Na][Na] (Na = Np_fwd+1); Phia [nq][Na] adjoint basis at the Gauss
  * points; Pext [nq][Np_fwd] forward basis at the points adj_march.m:79 evaluates;
  * Ifa [Na][Np_fwd] forward basis at the adjoint nodes; wq [nq].  V[(k*Na + i)*n_ics + ic],
- * err[ic*n_slabs + k]. */
+ * err[ic*n_slabs + k].
+ * Alias: not checked by the library; the inputs may overlap one another, V and err must
+ * overlap nothing (the caller's duty). */
 int dg_time_adjoint(int Np_fwd, int nq, const double* Sa, const double* Ma, const double* Phia,
                     const double* Pext, const double* Ifa, const double* wq, int n_slabs,
                     const double* times, int64_t n_ics, const double* y0, const double* Y,
@@ -620,7 +657,9 @@ int dg_time_adjoint(int Np_fwd, int nq, const double* Sa, const double* Ma, cons
  * t_coarse [n_steps+1] and t_fine [n_steps*ref_factor+1] are the cumulative times of
  * interpU (:27-28); interp_code [n_steps*ref_factor+1] says where np.interp takes each fine
  * value (j >= 0: interval j; -(j+1): node j exactly).  Outputs: U[n*n_ics + ic] (coarse
- * solution), V (nullable) [n*n_ics + ic] (fine adjoint), err_steps[ic*n_steps + r]. */
+ * solution), V (nullable) [n*n_ics + ic] (fine adjoint), err_steps[ic*n_steps + r].
+ * Alias: not checked by the library; the inputs may overlap one another, U, V and err_steps
+ * must overlap nothing (the caller's duty). */
 int dg_fd_adapt_sweep(int n_steps, int ref_factor, const double* dt_n, const double* t_coarse,
                       const double* t_fine, const int32_t* interp_code, const double* u0,
                       int64_t n_ics, double* U, double* V, double* err_steps, void* stream);
@@ -643,7 +682,9 @@ enum { DG_RESNET_MAX_LAYERS = 256 };
  * solution (refineSolution, :117-122): t_coarse, t_fine and interp_code as for
  * dg_fd_adapt_sweep.  ref_factor 2..16.  Outputs: U[n*n_ics + ic] (coarse solution),
  * V (nullable) [n*n_ics + ic] (fine adjoint), err_steps[ic*n_layers + i] (for dg_sum_rows:
- * the mean over members of :479). */
+ * the mean over members of :479).
+ * Alias: not checked by the library; the inputs may overlap one another, U, V and err_steps
+ * must overlap nothing (the caller's duty). */
 int dg_resnet_adapt_sweep(int n_layers, int ref_factor, const int32_t* offsets,
                           const double* bias, const double* w1, const double* w2,
                           const double* dt_n, const double* t_coarse, const double* t_fine,
@@ -660,7 +701,9 @@ int dg_resnet_grad_scratch(int n_layers, const int32_t* offsets, int64_t n_ics, 
  * are bit-reproducible (no floating-point atomics): members are cut into chunks of 256 in
  * ascending order; a chunk's gradient terms are added in ascending member order (its losses by
  * a stride-halving tree: 128, 64, .., 1); the chunk sums are added in ascending chunk order;
- * one division by n_ics follows. */
+ * one division by n_ics follows.
+ * Alias: not checked by the library; the inputs may overlap one another, loss_ic, loss_mean,
+ * grad and scratch must overlap nothing (the caller's duty). */
 int dg_resnet_loss_grad(int n_layers, const int32_t* offsets, const double* bias,
                         const double* w1, const double* w2, const double* dt_n, const double* u0,
                         const double* target, int64_t n_ics, double* loss_ic, double* loss_mean,

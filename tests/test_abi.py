@@ -92,3 +92,65 @@ def test_tuning_a_null_plan_is_an_argument_error(pkg):
     assert lib.dg_plan_tune(None, key, 2) == pkg._lib.DG_ERR_ARG
   out = (ctypes.c_int64 * 4)()
   assert lib.dg_plan_query_rec(None, out) == pkg._lib.DG_ERR_ARG
+
+
+def entry_point_comments():
+  """name -> (parameter list, the comment block that precedes its declaration) for every
+  function of the header; declarations that follow one another share the block above them."""
+  src = open(HEADER).read()
+  out, comment = {}, ""
+  for m in re.finditer(r"/\*(.*?)\*/|^\s*(?:const\s+)?[A-Za-z_][\w\s\*]*?\b(dg_\w+)\s*\(([^;]*?)\)\s*;",
+                       src, flags=re.S | re.M):
+    if m.group(2) is None:
+      comment = m.group(1)
+    else:
+      out[m.group(2)] = (m.group(3), comment)
+  return out
+
+
+# Entry points whose aliasing differs from the default sentence of the Conventions block: each
+# says how in an "Alias:" (or, in a shared comment, "Alias (name):") line.
+ALIAS_LINES = {"dg_lserk4_fwd", "dg_lserk4_fwd_ex", "dg_lserk4_adj", "dg_lserk4_adj_ex",
+               "dg_lserk4_fwd_rec", "dg_plan_refine_marked", "dg_init_sine", "dg_time_march",
+               "dg_time_adjoint", "dg_fd_adapt_sweep", "dg_resnet_adapt_sweep",
+               "dg_resnet_loss_grad"}
+
+
+def test_header_states_the_alias_rule_for_every_entry_point():
+  """The Conventions block has the "Aliasing and alignment" paragraph with the default (disjoint
+  byte ranges, half-open, DG_ERR_ARG before anything is enqueued), and every compute entry point
+  (one with a stream) that takes two or more arrays either has its own Alias line -- exactly the
+  entry points listed above -- or falls under that default."""
+  src = open(HEADER).read()
+  head = src[:src.index("#ifndef DG_ADVEC_H")]
+  para = head[head.index("Aliasing and alignment"):]
+  flat = " ".join(para.replace("*", " ").split())
+  for phrase in ("byte ranges of any two array arguments of one compute call must be disjoint",
+                 'unless that entry point\'s comment has an "Alias:" line', "half-open",
+                 "exact identity", "DG_ERR_ARG before anything is enqueued", "16 bytes"):
+    assert phrase in flat, phrase
+  fns = entry_point_comments()
+  assert set(fns) == set(declared_functions())
+  with_line, default = set(), set()
+  for name, (params, comment) in fns.items():
+    args = [a.strip() for a in params.split(",")]
+    if not any(re.fullmatch(r"void\s*\*\s*stream", a) for a in args):
+      continue  # not a compute call
+    arrays = [a for a in args if ("*" in a or "[" in a) and "dg_plan" not in a
+              and not re.fullmatch(r"void\s*\*\s*stream", a)]
+    if len(arrays) < 2:
+      continue
+    tagged = re.findall(r"Alias(?: \((\w+)\))?:", comment)
+    if "" in tagged or name in tagged:
+      with_line.add(name)
+    else:
+      default.add(name)
+  assert with_line == ALIAS_LINES, (sorted(with_line - ALIAS_LINES), sorted(ALIAS_LINES - with_line))
+  # the default covers the rest: the ones the library checks with its one range helper
+  for name in ("dg_advec_rhs", "dg_lserk4_adj_rec", "dg_lserk4_sweep_rec", "dg_lserk4_sweep_refine",
+               "dg_slope_limit_n", "dg_slope_limit_1", "dg_prolong", "dg_lserk4_adj_p",
+               "dg_lserk4_adj_p_refine", "dg_lserk4_sweep_p", "dg_plan_mark", "dg_sum_rows",
+               "dg_slice_candidate", "dg_argmax", "dg_argmax_ex", "dg_candidates_argmax",
+               "dg_stream_copy", "dg_plan_refine", "dg_field_to_children",
+               "dg_field_from_children"):
+    assert name in default, name
