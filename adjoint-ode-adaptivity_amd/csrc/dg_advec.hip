@@ -802,68 +802,57 @@ int launch_adj_e(const dg_plan* p, const double* win, double* wout, const double
 // Instantiated shapes: tile width W in {1, 2} (256 or 512 elements per tile) x steps per
 // launch in {1, 2, 4}, plus 8 steps per launch on 512-element tiles; 4 and 8 steps per
 // launch only for Np <= 8 (at Np = 9 hipcc/ROCm 7.2 fails instruction selection for the
-// 4-step shape; effective_msteps() never asks for them there).
-template <int NP, int NS>
-int launch_step_t(const dg_plan* p, int ms, const double* in, double* snap, double* last,
-                  const double* times, double dt, hipStream_t st) {
-  const bool w2 = p->tile_width == 2;
+// 4-step shape; effective_msteps() and rec_msteps_cap() never ask for them there).
+// f(integral_constant W, integral_constant MS) -> int.
+template <int N> using ic = std::integral_constant<int, N>;
+template <int NP, class F> int tile_shape(bool w2, int ms, F&& f) {
   if constexpr (NP <= 8) {
-    if (ms == 8) return launch_step_e<NP, NS, 2, 8>(p, in, snap, last, times, dt, st);
-    if (ms == 4 && w2) return launch_step_e<NP, NS, 2, 4>(p, in, snap, last, times, dt, st);
-    if (ms == 4) return launch_step_e<NP, NS, 1, 4>(p, in, snap, last, times, dt, st);
+    if (ms == 8) return f(ic<2>{}, ic<8>{});
+    if (ms == 4) return w2 ? f(ic<2>{}, ic<4>{}) : f(ic<1>{}, ic<4>{});
   }
-  if (ms == 2 && w2) return launch_step_e<NP, NS, 2, 2>(p, in, snap, last, times, dt, st);
-  if (ms == 2) return launch_step_e<NP, NS, 1, 2>(p, in, snap, last, times, dt, st);
-  if (w2) return launch_step_e<NP, NS, 2, 1>(p, in, snap, last, times, dt, st);
-  return launch_step_e<NP, NS, 1, 1>(p, in, snap, last, times, dt, st);
+  if (ms == 2) return w2 ? f(ic<2>{}, ic<2>{}) : f(ic<1>{}, ic<2>{});
+  return w2 ? f(ic<2>{}, ic<1>{}) : f(ic<1>{}, ic<1>{});
 }
 
-template <int NP, int NS>
-int launch_adj_t(const dg_plan* p, int ms, const double* win, double* wout, const double* snap,
-                 double* eta, int em, const double* t_next, const double* src, double dt,
-                 hipStream_t st) {
-  const bool w2 = p->tile_width == 2;
-  if constexpr (NP <= 8) {
-    if (ms == 8)
-      return launch_adj_e<NP, NS, 2, 8>(p, win, wout, snap, eta, em, t_next, src, dt, st);
-    if (ms == 4 && w2)
-      return launch_adj_e<NP, NS, 2, 4>(p, win, wout, snap, eta, em, t_next, src, dt, st);
-    if (ms == 4)
-      return launch_adj_e<NP, NS, 1, 4>(p, win, wout, snap, eta, em, t_next, src, dt, st);
-  }
-  if (ms == 2 && w2)
-    return launch_adj_e<NP, NS, 2, 2>(p, win, wout, snap, eta, em, t_next, src, dt, st);
-  if (ms == 2)
-    return launch_adj_e<NP, NS, 1, 2>(p, win, wout, snap, eta, em, t_next, src, dt, st);
-  if (w2) return launch_adj_e<NP, NS, 2, 1>(p, win, wout, snap, eta, em, t_next, src, dt, st);
-  return launch_adj_e<NP, NS, 1, 1>(p, win, wout, snap, eta, em, t_next, src, dt, st);
+template <int NP, int NS, bool REC = false>
+int launch_step_t(const dg_plan* p, bool w2, int ms, const double* in, double* snap, double* last,
+                  const double* times, double dt, hipStream_t st, RecPos pos = {}) {
+  return tile_shape<NP>(w2, ms, [&](auto w, auto m) -> int {
+    return launch_step_e<NP, NS, w, m, REC>(p, in, snap, last, times, dt, st, pos);
+  });
 }
 
-int launch_step(const dg_plan* p, int ms, const double* in, double* snap, double* last,
-                const double* times, double dt, hipStream_t st) {
-  int rc = DG_OK;
-  if (p->lane_elems != 0 && p->nstages == 5 && p->NP <= 8)
+template <int NP, int NS, bool REC = false>
+int launch_adj_t(const dg_plan* p, bool w2, int ms, const double* win, double* wout,
+                 const double* snap, double* eta, int em, const double* t_next,
+                 const double* src, double dt, hipStream_t st, int64_t n0 = 0) {
+  return tile_shape<NP>(w2, ms, [&](auto w, auto m) -> int {
+    return launch_adj_e<NP, NS, w, m, REC>(p, win, wout, snap, eta, em, t_next, src, dt, st, n0);
+  });
+}
+
+// One forward launch of ms steps on wave tiles (lane_elems != 0, LSERK4, Np <= 8) or on the
+// stage-loop workgroup tiles of the plan's width.
+int launch_step(const dg_plan* p, int lane_elems, int ms, const double* in, double* snap,
+                double* last, const double* times, double dt, hipStream_t st) {
+  if (lane_elems != 0 && p->nstages == 5 && p->NP <= 8)
     return wave_launch_step(p, ms, in, snap, last, times, dt, st);
-  if (p->nstages == 5) {
-    DG_DISPATCH_NP(p->NP, rc = (launch_step_t<NP, 5>(p, ms, in, snap, last, times, dt, st)));
-  } else {
-    DG_DISPATCH_NP(p->NP, rc = (launch_step_t<NP, 1>(p, ms, in, snap, last, times, dt, st)));
-  }
-  return rc;
+  const bool w2 = p->tile_width == 2;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    if (p->nstages == 5) return launch_step_t<np, 5>(p, w2, ms, in, snap, last, times, dt, st);
+    return launch_step_t<np, 1>(p, w2, ms, in, snap, last, times, dt, st);
+  });
 }
 
 int launch_adj(const dg_plan* p, int ms, const double* win, double* wout, const double* snap,
                double* eta, int em, const double* t_next, const double* src, double dt,
                hipStream_t st) {
-  int rc = DG_OK;
-  if (p->nstages == 5) {
-    DG_DISPATCH_NP(p->NP, rc = (launch_adj_t<NP, 5>(p, ms, win, wout, snap, eta, em, t_next, src,
-                                                    dt, st)));
-  } else {
-    DG_DISPATCH_NP(p->NP, rc = (launch_adj_t<NP, 1>(p, ms, win, wout, snap, eta, em, t_next, src,
-                                                    dt, st)));
-  }
-  return rc;
+  const bool w2 = p->tile_width == 2;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    if (p->nstages == 5)
+      return launch_adj_t<np, 5>(p, w2, ms, win, wout, snap, eta, em, t_next, src, dt, st);
+    return launch_adj_t<np, 1>(p, w2, ms, win, wout, snap, eta, em, t_next, src, dt, st);
+  });
 }
 
 // Record sweeps run on pair tiles (dg_rec.hip), Np <= 9, unless DG_TUNE_REC_LANE_ELEMENTS = 1
@@ -908,72 +897,48 @@ inline int rec_msteps_fwd(const dg_plan* p) {
   return rec_msteps_cap(p, m ? m : p->rec_msteps, rec_fwd_width(p));
 }
 
-// Jump-record launches: LSERK4 (NS = 5) on the workgroup tiles, the plan's tile width and
-// steps per launch (the 8-step shape on 512-element tiles; Np = 9 at most 2 steps).
-template <int NP>
-int launch_step_rec_t(const dg_plan* p, int ms, const double* in, double* rec, double* last,
-                      const double* times, double dt, hipStream_t st, RecPos pos) {
+// Jump-record launches: on pair tiles, or LSERK4 (NS = 5) on the workgroup tiles at the
+// record's tile width and steps per launch.
+int launch_step_rec(const dg_plan* p, int ms, const double* in, double* rec, double* last,
+                    const double* times, double dt, hipStream_t st, RecPos pos) {
   if (rec_pairs(p))
     return pair_launch_step_rec(p, ms, in, rec, last, times, dt, st, pos.n0, pos.jend);
-  const bool w2 = rec_fwd_width(p) == 2;
-  if constexpr (NP <= 8) {
-    if (ms == 8) return launch_step_e<NP, 5, 2, 8, true>(p, in, rec, last, times, dt, st, pos);
-    if (ms == 4 && w2) return launch_step_e<NP, 5, 2, 4, true>(p, in, rec, last, times, dt, st, pos);
-    if (ms == 4) return launch_step_e<NP, 5, 1, 4, true>(p, in, rec, last, times, dt, st, pos);
-  }
-  if (ms == 2 && w2) return launch_step_e<NP, 5, 2, 2, true>(p, in, rec, last, times, dt, st, pos);
-  if (ms == 2) return launch_step_e<NP, 5, 1, 2, true>(p, in, rec, last, times, dt, st, pos);
-  if (w2) return launch_step_e<NP, 5, 2, 1, true>(p, in, rec, last, times, dt, st, pos);
-  return launch_step_e<NP, 5, 1, 1, true>(p, in, rec, last, times, dt, st, pos);
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    return launch_step_t<np, 5, true>(p, rec_fwd_width(p) == 2, ms, in, rec, last, times, dt, st,
+                                      pos);
+  });
 }
 
-template <int NP>
-int launch_adj_rec_t(const dg_plan* p, int ms, const double* win, double* wout, const double* rec,
-                     double* eta, int em, const double* t_next, const double* src, double dt,
-                     hipStream_t st, int64_t n0) {
+int launch_adj_rec(const dg_plan* p, int ms, const double* win, double* wout, const double* rec,
+                   double* eta, int em, const double* t_next, const double* src, double dt,
+                   hipStream_t st, int64_t n0) {
   if (rec_pairs(p))
     return pair_launch_adj_rec(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-  const bool w2 = p->rec_tile_width == 2;
-  if constexpr (NP <= 8) {
-    if (ms == 8)
-      return launch_adj_e<NP, 5, 2, 8, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
-    if (ms == 4 && w2)
-      return launch_adj_e<NP, 5, 2, 4, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
-    if (ms == 4)
-      return launch_adj_e<NP, 5, 1, 4, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
-  }
-  if (ms == 2 && w2)
-    return launch_adj_e<NP, 5, 2, 2, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
-  if (ms == 2)
-    return launch_adj_e<NP, 5, 1, 2, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
-  if (w2) return launch_adj_e<NP, 5, 2, 1, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
-  return launch_adj_e<NP, 5, 1, 1, true>(p, win, wout, rec, eta, em, t_next, src, dt, st, n0);
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    return launch_adj_t<np, 5, true>(p, p->rec_tile_width == 2, ms, win, wout, rec, eta, em,
+                                     t_next, src, dt, st, n0);
+  });
 }
 
 // Steps per launch the plan's shape allows: 8 only with 512-element tiles (the cone is
 // 8*NS elements per side) and Np <= 8; at Np = 9 at most 2 (hipcc/ROCm 7.2 fails
 // instruction selection for the 4-step shape there).
-inline int effective_msteps(const dg_plan* p) {
-  int m = p->msteps;
-  if (m == 8 && !(p->tile_width == 2 || p->lane_elems == 8)) m = 4;
-  if (m == 8 && p->lane_elems == 2) m = 4;  // 128-element wave tiles: cone too wide
+inline int effective_msteps(const dg_plan* p, FwdShape s) {
+  int m = s.msteps;
+  if (m == 8 && !(p->tile_width == 2 || s.lane_elems == 8)) m = 4;
+  if (m == 8 && s.lane_elems == 2) m = 4;  // 128-element wave tiles: cone too wide
   if (p->NP > 8 && m > 2) m = 2;
   return m;
 }
+inline FwdShape plan_shape(const dg_plan* p) { return {p->msteps, p->lane_elems, p->snap_pairs}; }
 
-// Steps per launch of the next chunk of a jump-record sweep (halving the plan's setting).
-inline int chunk_rec(const dg_plan* p, int left, bool fwd = false) {
-  int m = fwd ? rec_msteps_fwd(p) : rec_msteps(p);
-  while (m > left) m >>= 1;
-  return m < 1 ? 1 : m;
+// The chunk functions (dg_chain.h) of the linear sweeps, halving the plan's setting: the
+// snapshot sweeps' ({8, 4, 2, 1}) and the jump-record sweeps' (20 -> 10 -> 5 -> 2 -> 1).
+inline auto chunk(const dg_plan* p, FwdShape s) {
+  return [m0 = effective_msteps(p, s)](int left) { return chain::halve(m0, left); };
 }
-
-// Steps per launch for the next chunk of `left` steps (greedy over {4, 2, 1}, capped by
-// the plan's setting).
-inline int chunk(const dg_plan* p, int left) {
-  int m = effective_msteps(p);
-  while (m > left) m >>= 1;
-  return m < 1 ? 1 : m;
+inline auto chunk_rec(const dg_plan* p, bool fwd) {
+  return [m0 = fwd ? rec_msteps_fwd(p) : rec_msteps(p)](int left) { return chain::halve(m0, left); };
 }
 
 // The dataflow sweep's blocks for `nsteps` steps (dg_sweep.hip): true with the forward /
@@ -1033,6 +998,31 @@ bool sweep_shape(const dg_plan* p, int nsteps, int* waves, int* msf, int* msa) {
 }  // namespace
 
 namespace dgk {
+int axpy_copy(const double* w, const double* u, double c, double* out, int64_t n,
+              hipStream_t st) {
+  hipLaunchKernelGGL(k_axpy_copy, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, w, u, c, out, n);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int fwd_march(const dg_plan* p, FwdShape s, double* u, const double* tn, double dt, int nsteps,
+              double* snapshots, hipStream_t st) {
+  const int64_t field = p->ktot * p->NP;
+  if (s.snap_pairs && p->nstages == 5)
+    // Horner-form pair tiles (k_step_rps): every state from the registers, the launch's last
+    // through LDS; no `last` output, and the plan's steps per launch uncapped
+    return chain::march(
+        nsteps, [m0 = s.msteps](int left) { return chain::halve(m0, left); }, u, snapshots, field,
+        false, field_copy(field, st),
+        [&](int, int n, int m, const double* in, double* rows, double*) {
+          return pair_launch_step_snap(p, m, in, rows, &tn[n], dt, st);
+        });
+  return chain::march(nsteps, chunk(p, s), u, snapshots, field, true, field_copy(field, st),
+                      [&](int, int n, int m, const double* in, double* rows, double* last) {
+                        return launch_step(p, s.lane_elems, m, in, rows, last, &tn[n], dt, st);
+                      });
+}
+
 int sweep_scratch(dg_plan* p, size_t sync_bytes, size_t data_bytes, hipStream_t st, char** data) {
   const size_t sync = sync_bytes > p->sweep_sync ? sync_bytes : p->sweep_sync;
   if (!p->d_sweep || p->sweep_bytes < sync + data_bytes) {
@@ -1124,7 +1114,13 @@ int dg_plan_create(int N, int64_t K, int64_t batch, const double* r, const doubl
   std::memcpy(p->LIFT, LIFT, sizeof(double) * NP * 2);
 
   bool sym = false;
-  DG_DISPATCH_NP(p->NP, sym = make_eo<NP>(p, 1.0, nullptr));
+  if (const int rc = dispatch_np(p->NP, [&](auto np) -> int {
+        sym = make_eo<np>(p, 1.0, nullptr);
+        return DG_OK;
+      })) {
+    delete p;
+    return rc;
+  }
   if (!sym) {
     delete p;
     return fail(DG_ERR_ARG, "Dr/LIFT are not centro-(anti)symmetric (nodes must be symmetric)");
@@ -1310,7 +1306,7 @@ int dg_plan_query(const dg_plan* p, int64_t out[8]) {
   out[4] = p->uniform ? 1 : 0;
   out[5] = p->nstages;
   out[6] = p->tile_width;
-  out[7] = effective_msteps(p);
+  out[7] = effective_msteps(p, plan_shape(p));
   return DG_OK;
 }
 
@@ -1561,11 +1557,12 @@ int dg_advec_rhs(const dg_plan* p, const double* u, double* rhs, double t, void*
   const double uin = inflow_value(p, t);
   const unsigned grid = grid_for(p->ktot, kBlock);
   const double* sc = p->uniform ? nullptr : p->d_scale;
-  DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_rhs<NP>), dim3(grid), dim3(kBlock), 0, st, u, rhs,
-                                           sc, make_op<NP>(p), p->s_uniform, uin, p->ktot,
-                                           int32_t(p->K)));
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    hipLaunchKernelGGL((k_rhs<np>), dim3(grid), dim3(kBlock), 0, st, u, rhs, sc, make_op<np>(p),
+                       p->s_uniform, uin, p->ktot, int32_t(p->K));
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 int dg_lserk4_fwd(dg_plan* p, double* u, double t0, double dt, int nsteps, double* snapshots,
@@ -1594,59 +1591,14 @@ int dg_lserk4_fwd_ex(dg_plan* p, double* u, double t0, double dt, int nsteps, do
   }
   if (p->nonlinear())
     return nl_fwd(p, u, t0, dt, nsteps, snapshots, p->limiter ? decisions : nullptr, st);
-  // Time levels by repeated addition (time = time + dt, One_code.mlx:139).
-  std::vector<double> tn(size_t(nsteps) + 1);
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
-  if (snapshots && p->snap_pairs && p->nstages == 5) {
-    // Horner-form pair tiles (k_step_rps): every state from the registers, the launch's last
-    // through LDS; u receives u^N by a copy when it is not snapshot 0
-    if (snapshots != u)
-      HIP_TRY(hipMemcpyAsync(snapshots, u, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
-    for (int n = 0; n < nsteps;) {
-      int m = p->msteps;
-      while (m > nsteps - n) m >>= 1;
-      if (const int rc = pair_launch_step_snap(p, m, snapshots + int64_t(n) * field,
-                                               snapshots + int64_t(n + 1) * field, &tn[n], dt, st))
-        return rc;
-      n += m;
-    }
-    if (snapshots != u)
-      HIP_TRY(hipMemcpyAsync(u, snapshots + int64_t(nsteps) * field, sizeof(double) * field,
-                             hipMemcpyDeviceToDevice, st));
-    return DG_OK;
-  }
-  if (snapshots) {
-    if (snapshots != u)
-      HIP_TRY(hipMemcpyAsync(snapshots, u, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
-    for (int n = 0; n < nsteps;) {
-      const int m = chunk(p, nsteps - n);
-      double* last = (n + m == nsteps && snapshots != u) ? u : nullptr;
-      const int rc = launch_step(p, m, snapshots + int64_t(n) * field,
-                                 snapshots + int64_t(n + 1) * field, last, &tn[n], dt, st);
-      if (rc) return rc;
-      n += m;
-    }
-    return DG_OK;
-  }
-  // Ping-pong between u and the plan scratch; if the launch count is odd the first launch
-  // reads a scratch copy of u so that the last one lands in u.
-  int launches = 0;
-  for (int n = 0; n < nsteps; n += chunk(p, nsteps - n)) ++launches;
-  double* a = u;
-  double* b = p->d_scratch;
-  if (launches % 2 == 1) {
-    HIP_TRY(hipMemcpyAsync(b, a, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
-    std::swap(a, b);
-  }
-  for (int n = 0; n < nsteps;) {
-    const int m = chunk(p, nsteps - n);
-    const int rc = launch_step(p, m, a, nullptr, b, &tn[n], dt, st);
-    if (rc) return rc;
-    std::swap(a, b);
-    n += m;
-  }
-  return DG_OK;
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
+  const FwdShape s = plan_shape(p);
+  if (snapshots) return fwd_march(p, s, u, tn.data(), dt, nsteps, snapshots, st);
+  return chain::pingpong(nsteps, chunk(p, s), u, p->d_scratch, field_copy(field, st),
+                         [&](int, int n, int m, const double* in, double* out) {
+                           return launch_step(p, s.lane_elems, m, in, nullptr, out, &tn[n], dt,
+                                              st);
+                         });
 }
 
 int dg_lserk4_adj(dg_plan* p, double* w, const double* snapshots, double t0, double dt,
@@ -1677,40 +1629,21 @@ int dg_lserk4_adj_ex(dg_plan* p, double* w, const double* snapshots, double t0, 
     return nl_adj(p, w, snapshots, t0, dt, nsteps, src_coef, eta, flags,
                   p->limiter ? decisions : nullptr, st);
   const int64_t field = p->ktot * p->NP;
-  // Same time levels as the forward sweep (repeated addition).
-  std::vector<double> tn(size_t(nsteps) + 1), src(size_t(nsteps) + 1, src_coef);
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
+  std::vector<double> src(size_t(nsteps) + 1, src_coef);
   src[nsteps] = 0.0;  // left-endpoint rule: no source at the terminal node
-  // Launch l reads buf[l] and writes buf[l+1]: buf[0] = w, the last output = w, and the
-  // intermediate states alternate between the two plan scratch fields.  (w may alias the
-  // terminal snapshot: only the first launch reads snapshot nsteps.)
-  int launches = 0;
-  for (int n = nsteps; n > 0; n -= chunk(p, n)) ++launches;
-  int l = 0;
-  const double* in = w;
-  for (int n = nsteps; n > 0; ++l) {  // this launch covers steps n-m .. n-1
-    const int m = chunk(p, n);
-    const int n0 = n - m;
-    // (a single launch cannot write its own input: it goes through scratch and back)
-    double* out = (l == launches - 1 && launches > 1)
-                      ? w : ((l % 2 == 0) ? p->d_scratch : p->d_scratch2);
-    // DG_ADJ_ETA_ASSIGN: the sweep's first launch assigns eta; DG_ADJ_ETA_ABS: its last
-    // launch stores |eta|.
-    const int em = ((l == 0 && (flags & DG_ADJ_ETA_ASSIGN)) ? kEtaAssign : 0) |
-                   ((n0 == 0 && (flags & DG_ADJ_ETA_ABS)) ? kEtaAbs : 0);
-    const int rc = launch_adj(p, m, in, out, snapshots + int64_t(n0 + 1) * field, eta, em,
-                              &tn[n0 + 1], &src[n0 + 1], dt, st);
-    if (rc) return rc;
-    in = out;
-    n = n0;
-  }
+  // (w may alias the terminal snapshot: only the first launch reads snapshot nsteps)
+  const chain::Result r = chain::reverse(
+      nsteps, chunk(p, plan_shape(p)), w, p->d_scratch, p->d_scratch2,
+      flags & DG_ADJ_ETA_ASSIGN, flags & DG_ADJ_ETA_ABS,
+      [&](int, int n0, int m, const double* in, double* out, int em) {
+        return launch_adj(p, m, in, out, snapshots + int64_t(n0 + 1) * field, eta, em,
+                          &tn[n0 + 1], &src[n0 + 1], dt, st);
+      });
+  if (r.rc) return r.rc;
   // Node-0 source K^0 = src * u^0 (and the hand-back of a single-launch sweep).
-  if ((src_coef != 0.0 && nsteps > 0) || in != w) {
-    hipLaunchKernelGGL(k_axpy_copy, dim3(grid_for(field, kBlock)), dim3(kBlock), 0, st, in,
-                       snapshots, nsteps > 0 ? src_coef : 0.0, w, field);
-    HIP_TRY(hipGetLastError());
-  }
+  if ((src_coef != 0.0 && nsteps > 0) || r.buf != w)
+    return axpy_copy(r.buf, snapshots, nsteps > 0 ? src_coef : 0.0, w, field, st);
   return DG_OK;
 }
 
@@ -1736,31 +1669,17 @@ int dg_lserk4_fwd_rec(dg_plan* p, const double* u0, double* uN, double t0, doubl
       HIP_TRY(hipMemcpyAsync(uN, u0, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
     return DG_OK;
   }
-  std::vector<double> tn(size_t(nsteps) + 1);  // time = time + dt (One_code.mlx:139)
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
-  // Launch l reads in_l and writes the next state: the last launch lands in uN, the others
-  // alternate between the two plan scratch fields (a launch never writes its own input, so
-  // u0 == uN is allowed and u0 is otherwise left untouched).
-  int launches = 0;
-  for (int n = 0; n < nsteps; n += chunk_rec(p, nsteps - n, true)) ++launches;
-  const double* in = u0;
-  int l = 0;
-  for (int n = 0; n < nsteps; ++l) {
-    const int m = chunk_rec(p, nsteps - n, true);
-    const bool final = (n + m == nsteps);
-    double* out = (final && in != uN) ? uN : ((l % 2 == 0) ? p->d_scratch : p->d_scratch2);
-    RecPos pos;
-    pos.n0 = n;
-    pos.jend = final;
-    int rc = DG_OK;
-    DG_DISPATCH_NP(p->NP, rc = launch_step_rec_t<NP>(p, m, in, jumps, out, &tn[n], dt, st, pos));
-    if (rc) return rc;
-    in = out;
-    n += m;
-  }
-  if (in != uN)  // (a one-launch in-place sweep went through scratch)
-    HIP_TRY(hipMemcpyAsync(uN, in, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
+  // (a launch never writes its own input, so u0 == uN is allowed and u0 is otherwise left
+  // untouched)
+  const chain::Result r = chain::forward(
+      nsteps, chunk_rec(p, true), u0, uN, p->d_scratch, p->d_scratch2,
+      [&](int, int n, int m, const double* in, double* out) {
+        return launch_step_rec(p, m, in, jumps, out, &tn[n], dt, st, RecPos{n, n + m == nsteps});
+      });
+  if (r.rc) return r.rc;
+  if (r.buf != uN)  // (a one-launch in-place sweep went through scratch)
+    return field_copy(field, st)(uN, r.buf);
   return DG_OK;
 }
 
@@ -1784,29 +1703,16 @@ int dg_lserk4_adj_rec(dg_plan* p, double* w, const double* jumps, double t0, dou
     return rc;
   if (eta != nullptr && nsteps == 0 && (flags & DG_ADJ_ETA_ASSIGN))
     HIP_TRY(hipMemsetAsync(eta, 0, sizeof(double) * p->ktot, st));
-  std::vector<double> tn(size_t(nsteps) + 1), src(size_t(nsteps) + 1, 0.0);
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
-  int launches = 0;
-  for (int n = nsteps; n > 0; n -= chunk_rec(p, n)) ++launches;
-  int l = 0;
-  const double* in = w;
-  for (int n = nsteps; n > 0; ++l) {  // this launch covers steps n-m .. n-1
-    const int m = chunk_rec(p, n);
-    const int n0 = n - m;
-    double* out = (l == launches - 1 && launches > 1)
-                      ? w : ((l % 2 == 0) ? p->d_scratch : p->d_scratch2);
-    const int em = ((l == 0 && (flags & DG_ADJ_ETA_ASSIGN)) ? kEtaAssign : 0) |
-                   ((n0 == 0 && (flags & DG_ADJ_ETA_ABS)) ? kEtaAbs : 0);
-    int rc = DG_OK;
-    DG_DISPATCH_NP(p->NP, rc = launch_adj_rec_t<NP>(p, m, in, out, jumps, eta, em, &tn[n0 + 1],
-                                                    &src[n0 + 1], dt, st, n0));
-    if (rc) return rc;
-    in = out;
-    n = n0;
-  }
-  if (in != w)
-    HIP_TRY(hipMemcpyAsync(w, in, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
+  const std::vector<double> src(size_t(nsteps) + 1, 0.0);
+  const chain::Result r = chain::reverse(
+      nsteps, chunk_rec(p, false), w, p->d_scratch, p->d_scratch2, flags & DG_ADJ_ETA_ASSIGN,
+      flags & DG_ADJ_ETA_ABS, [&](int, int n0, int m, const double* in, double* out, int em) {
+        return launch_adj_rec(p, m, in, out, jumps, eta, em, &tn[n0 + 1], &src[n0 + 1], dt, st,
+                              n0);
+      });
+  if (r.rc) return r.rc;
+  if (r.buf != w) return field_copy(field, st)(w, r.buf);
   return DG_OK;
 }
 
@@ -1921,9 +1827,8 @@ int sweep_rec_impl(dg_plan* p, const double* u0, double* uN, double* w, double* 
   b.am_pi = idx ? reinterpret_cast<int64_t*>(am + am_parts) : nullptr;
   b.err_host = p->d_sweep_err;
   b.spin_limit = p->sweep_spin_limit;
-  const int mode = eta ? (kEtaOn | ((aflags & DG_ADJ_ETA_ASSIGN) ? kEtaAssign : 0) |
-                          ((aflags & DG_ADJ_ETA_ABS) ? kEtaAbs : 0))
-                       : 0;
+  const int mode = chain::eta_sweep_mode(eta != nullptr, aflags & DG_ADJ_ETA_ASSIGN,
+                                         aflags & DG_ADJ_ETA_ABS);
   return sweep_launch_rec(p, waves, msf, msa, b, t0, dt, nsteps, mode, st);
 }
 }  // namespace
@@ -2021,10 +1926,12 @@ int dg_slope_limit_n(dg_plan* p, const double* u, double* ulim, int32_t* ids, vo
     return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(p->ktot, kBlock - 2);
-  DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_limit<NP, false>), dim3(grid), dim3(kBlock), 0, st,
-                                           u, ulim, ids, p->d_VX, make_lim<NP>(p)));
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    hipLaunchKernelGGL((k_limit<np, false>), dim3(grid), dim3(kBlock), 0, st, u, ulim, ids, p->d_VX,
+                       make_lim<np>(p));
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 int dg_slope_limit_1(dg_plan* p, const double* u, double* ulim, void* stream) {
@@ -2033,10 +1940,12 @@ int dg_slope_limit_1(dg_plan* p, const double* u, double* ulim, void* stream) {
   if (const int rc = disjoint({{"u", u, fb}, {"ulim", ulim, fb}})) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(p->ktot, kBlock - 2);
-  DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_limit<NP, true>), dim3(grid), dim3(kBlock), 0, st,
-                                           u, ulim, nullptr, p->d_VX, make_lim<NP>(p)));
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    hipLaunchKernelGGL((k_limit<np, true>), dim3(grid), dim3(kBlock), 0, st, u, ulim, nullptr, p->d_VX,
+                       make_lim<np>(p));
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 int dg_argmax(dg_plan* p, const double* x, int64_t n, int use_abs, int64_t* idx, void* stream) {
@@ -2137,10 +2046,12 @@ int dg_init_sine(const dg_plan* p, const double* amp, const double* freq, const 
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(p->ktot, kBlock);
-  DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_init_sine<NP>), dim3(grid), dim3(kBlock), 0, st,
-                                           p->d_VX, amp, freq, phase, u, make_lim<NP>(p)));
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    hipLaunchKernelGGL((k_init_sine<np>), dim3(grid), dim3(kBlock), 0, st, p->d_VX, amp, freq,
+                       phase, u, make_lim<np>(p));
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 }  // extern "C"

@@ -380,13 +380,6 @@ __global__ __launch_bounds__(kBlock) void k_rhs_nl(const double* __restrict__ u,
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_src_copy(const double* __restrict__ w,
-                                                     const double* __restrict__ u, double c,
-                                                     double* __restrict__ out, int64_t n) {
-  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i < n) out[i] = fma(c, u[i], w[i]);
-}
-
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
@@ -485,9 +478,9 @@ int launch_nl_step(const dg_plan* p, int ms, const double* in, double* snap, dou
     const int rc = ow_step(p, in, snap, last, codes, times, dt, st);
     if (rc != 1) return rc;  // 1: no overlapped-wave kernel for this shape
   }
-  int rc = DG_OK;
-  DG_DISPATCH_NP(p->NP, rc = step_np<NP>(p, ms, in, snap, last, codes, times, dt, st));
-  return rc;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    return step_np<np>(p, ms, in, snap, last, codes, times, dt, st);
+  });
 }
 
 // Steps per limited-forward launch: 1 or 2 (the cone is 10 elements per step).  The
@@ -497,9 +490,9 @@ int launch_nl_step(const dg_plan* p, int ms, const double* in, double* snap, dou
 // and 2 without (A/B at K = 2^22: 82 against 88 µs per step with snapshots, 84 against 80.5
 // without).  An explicit msteps of 1 or 2 is kept.  The overlapped waves run 1 step per
 // launch (a 2-step window would own 24 of its 64 elements).
-inline int chunk_nl(const dg_plan* p, int left, bool snapshots) {
+inline auto chunk_nl(const dg_plan* p, bool snapshots) {
   const int m = (p->msteps == 2 || (p->msteps > 2 && !snapshots && !p->nl_exchange)) ? 2 : 1;
-  return m > left ? left : m;
+  return [m](int left) { return m > left ? left : m; };
 }
 
 }  // namespace
@@ -508,8 +501,8 @@ namespace dgk {
 
 int nl_query(const dg_plan* p, int64_t out[3]) {
   out[0] = p->nl_exchange;
-  out[1] = chunk_nl(p, 1 << 30, true);
-  out[2] = chunk_nl(p, 1 << 30, false);
+  out[1] = chunk_nl(p, true)(1 << 30);
+  out[2] = chunk_nl(p, false)(1 << 30);
   return DG_OK;
 }
 
@@ -517,59 +510,35 @@ int nl_rhs(const dg_plan* p, const double* u, double* rhs, double t, hipStream_t
   const double fin = flux_value(true, inflow_value(p, t));
   const unsigned grid = grid_for(p->ktot, kBlock);
   const double* sc = p->uniform ? nullptr : p->d_scale;
-  DG_DISPATCH_NP(p->NP, hipLaunchKernelGGL((k_rhs_nl<NP>), dim3(grid), dim3(kBlock), 0, st, u,
-                                           rhs, sc, make_op<NP>(p), p->s_uniform, fin, p->ktot,
-                                           int32_t(p->K)));
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    hipLaunchKernelGGL((k_rhs_nl<np>), dim3(grid), dim3(kBlock), 0, st, u, rhs, sc,
+                       make_op<np>(p), p->s_uniform, fin, p->ktot, int32_t(p->K));
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 int nl_fwd(dg_plan* p, double* u, double t0, double dt, int nsteps, double* snapshots,
            uint16_t* decisions, hipStream_t st) {
   const int64_t field = p->ktot * p->NP;
-  std::vector<double> tn(size_t(nsteps) + 1);  // time = time + dt (One_code.mlx:139)
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
-  if (snapshots) {
-    if (snapshots != u)
-      HIP_TRY(hipMemcpyAsync(snapshots, u, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
-    for (int n = 0; n < nsteps;) {
-      const int m = chunk_nl(p, nsteps - n, true);
-      double* last = (n + m == nsteps && snapshots != u) ? u : nullptr;
-      uint16_t* dec = decisions ? decisions + int64_t(n) * p->ktot : nullptr;
-      const int rc = launch_nl_step(p, m, snapshots + int64_t(n) * field,
-                                    snapshots + int64_t(n + 1) * field, last, dec, &tn[n], dt,
-                                    st);
-      if (rc) return rc;
-      n += m;
-    }
-    return DG_OK;
-  }
-  int launches = 0;  // ping-pong u <-> scratch, landing the last launch in u
-  for (int n = 0; n < nsteps; n += chunk_nl(p, nsteps - n, false)) ++launches;
-  double* a = u;
-  double* b = p->d_scratch;
-  if (launches % 2 == 1) {
-    HIP_TRY(hipMemcpyAsync(b, a, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
-    std::swap(a, b);
-  }
-  for (int n = 0; n < nsteps;) {
-    const int m = chunk_nl(p, nsteps - n, false);
-    uint16_t* dec = decisions ? decisions + int64_t(n) * p->ktot : nullptr;
-    const int rc = launch_nl_step(p, m, a, nullptr, b, dec, &tn[n], dt, st);
-    if (rc) return rc;
-    std::swap(a, b);
-    n += m;
-  }
-  return DG_OK;
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
+  auto dec = [&](int n) { return decisions ? decisions + int64_t(n) * p->ktot : nullptr; };
+  if (snapshots)
+    return chain::march(nsteps, chunk_nl(p, true), u, snapshots, field, true,
+                        field_copy(field, st),
+                        [&](int, int n, int m, const double* in, double* rows, double* last) {
+                          return launch_nl_step(p, m, in, rows, last, dec(n), &tn[n], dt, st);
+                        });
+  return chain::pingpong(nsteps, chunk_nl(p, false), u, p->d_scratch, field_copy(field, st),
+                         [&](int, int n, int m, const double* in, double* out) {
+                           return launch_nl_step(p, m, in, nullptr, out, dec(n), &tn[n], dt, st);
+                         });
 }
 
 int nl_adj(dg_plan* p, double* w, const double* snapshots, double t0, double dt, int nsteps,
            double src_coef, double* eta, int flags, const uint16_t* decisions, hipStream_t st) {
   const int64_t field = p->ktot * p->NP;
-  std::vector<double> tn(size_t(nsteps) + 1);
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
   // The troubled-tile list of k_adj_nl (shared by the steps: each step's wide pass has
   // finished before the next step lists) and one count per step, zeroed here once per sweep.
   // The overlapped-wave adjoint (DG_TUNE_NL_EXCHANGE; it needs the record when limited) lists
@@ -598,37 +567,30 @@ int nl_adj(dg_plan* p, double* w, const double* snapshots, double t0, double dt,
     counts = p->d_nl_list + p->nl_list_tiles;
     HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int32_t) * nsteps, st));
   }
-  // Launch for step n reads w^{n+1} and u^n and writes w^n; intermediate states alternate
-  // between the plan scratch fields and the last launch lands in w.  (w may alias the
-  // terminal snapshot: only the first launch reads w, and no launch reads snapshot nsteps.)
-  const double* in = w;
-  int l = 0;
-  for (int n = nsteps - 1; n >= 0; --n, ++l) {
-    double* out = (n == 0 && nsteps > 1) ? w : ((l % 2 == 0) ? p->d_scratch : p->d_scratch2);
-    const double src = (n + 1 == nsteps) ? 0.0 : src_coef;  // left-endpoint rule
-    // DG_ADJ_ETA_ASSIGN / DG_ADJ_ETA_ABS: first launch assigns eta, last one stores |eta|
-    const int em = ((l == 0 && (flags & DG_ADJ_ETA_ASSIGN)) ? kEtaAssign : 0) |
-                   ((n == 0 && (flags & DG_ADJ_ETA_ABS)) ? kEtaAbs : 0);
-    int rc = 1;
-    const uint16_t* dec = decisions ? decisions + int64_t(n) * p->ktot : nullptr;
-    if (ow)
-      rc = ow_adj(p, in, out, snapshots + int64_t(n) * field, eta, em, dec,
-                  counts ? counts + n : nullptr, tn[n], src, dt, st);
-    if (rc == 1) {
-      if (ow) return fail(DG_ERR_ARG, "config-3 adjoint: no overlapped-wave kernel for this shape");
-      DG_DISPATCH_NP(p->NP, rc = adj_np<NP>(p, in, out, snapshots + int64_t(n) * field, eta, em,
-                                            dec, counts ? counts + n : nullptr, tn[n], src, dt,
-                                            st));
-    }
-    if (rc) return rc;
-    in = out;
-  }
+  // One step per launch: the launch for step n reads w^{n+1} and u^n and writes w^n.  (w may
+  // alias the terminal snapshot: only the first launch reads w, and no launch reads snapshot
+  // nsteps.)
+  const chain::Result r = chain::reverse(
+      nsteps, [](int) { return 1; }, w, p->d_scratch, p->d_scratch2, flags & DG_ADJ_ETA_ASSIGN,
+      flags & DG_ADJ_ETA_ABS, [&](int, int n, int, const double* in, double* out, int em) {
+        const double src = (n + 1 == nsteps) ? 0.0 : src_coef;  // left-endpoint rule
+        const uint16_t* dec = decisions ? decisions + int64_t(n) * p->ktot : nullptr;
+        int32_t* count = counts ? counts + n : nullptr;
+        const double* snap = snapshots + int64_t(n) * field;
+        if (ow) {
+          const int rc = ow_adj(p, in, out, snap, eta, em, dec, count, tn[n], src, dt, st);
+          if (rc == 1)
+            return fail(DG_ERR_ARG, "config-3 adjoint: no overlapped-wave kernel for this shape");
+          return rc;
+        }
+        return dispatch_np(p->NP, [&](auto np) -> int {
+          return adj_np<np>(p, in, out, snap, eta, em, dec, count, tn[n], src, dt, st);
+        });
+      });
+  if (r.rc) return r.rc;
   // Node-0 source w^0 += src u^0 (and the hand-back of a single-launch sweep).
-  if ((src_coef != 0.0 && nsteps > 0) || in != w) {
-    hipLaunchKernelGGL(k_src_copy, dim3(grid_for(field, kBlock)), dim3(kBlock), 0, st, in,
-                       snapshots, nsteps > 0 ? src_coef : 0.0, w, field);
-    HIP_TRY(hipGetLastError());
-  }
+  if ((src_coef != 0.0 && nsteps > 0) || r.buf != w)
+    return axpy_copy(r.buf, snapshots, nsteps > 0 ? src_coef : 0.0, w, field, st);
   return DG_OK;
 }
 

@@ -395,28 +395,28 @@ namespace dgn {
 int ow_step(const dg_plan* p, const double* in, double* snap, double* last, uint16_t* codes,
             const double* times, double dt, hipStream_t st) {
   const bool burg = p->flux == DG_FLUX_BURGERS, lim = p->limiter != 0;
-  int rc = DG_OK;
-  if (burg && lim)
-    DG_DISPATCH_NP(p->NP, rc = (launch_step_ow<NP, true, true>(p, in, snap, last, codes, times, dt, st)))
-  else if (burg)
-    DG_DISPATCH_NP(p->NP, rc = (launch_step_ow<NP, true, false>(p, in, snap, last, codes, times, dt, st)))
-  else
-    DG_DISPATCH_NP(p->NP, rc = (launch_step_ow<NP, false, true>(p, in, snap, last, codes, times, dt, st)))
-  return rc;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    if (burg && lim)
+      return launch_step_ow<np, true, true>(p, in, snap, last, codes, times, dt, st);
+    if (burg) return launch_step_ow<np, true, false>(p, in, snap, last, codes, times, dt, st);
+    return launch_step_ow<np, false, true>(p, in, snap, last, codes, times, dt, st);
+  });
 }
 
 int ow_adj(const dg_plan* p, const double* win, double* wout, const double* snap, double* eta,
            int em, const uint16_t* codes, int32_t* count, double t_n, double src, double dt,
            hipStream_t st) {
   const bool burg = p->flux == DG_FLUX_BURGERS, lim = p->limiter != 0;
-  int rc = DG_OK;
-  if (burg && lim)
-    DG_DISPATCH_NP(p->NP, rc = (launch_adj_ow<NP, true, true>(p, win, wout, snap, eta, em, codes, count, t_n, src, dt, st)))
-  else if (burg)
-    DG_DISPATCH_NP(p->NP, rc = (launch_adj_ow<NP, true, false>(p, win, wout, snap, eta, em, codes, count, t_n, src, dt, st)))
-  else
-    DG_DISPATCH_NP(p->NP, rc = (launch_adj_ow<NP, false, true>(p, win, wout, snap, eta, em, codes, count, t_n, src, dt, st)))
-  return rc;
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    if (burg && lim)
+      return launch_adj_ow<np, true, true>(p, win, wout, snap, eta, em, codes, count, t_n, src,
+                                           dt, st);
+    if (burg)
+      return launch_adj_ow<np, true, false>(p, win, wout, snap, eta, em, codes, count, t_n, src,
+                                            dt, st);
+    return launch_adj_ow<np, false, true>(p, win, wout, snap, eta, em, codes, count, t_n, src, dt,
+                                          st);
+  });
 }
 
 }  // namespace dgn

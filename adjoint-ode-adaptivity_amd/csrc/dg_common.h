@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dg_advec.h"
+#include "dg_chain.h"
 
 namespace dgk {
 
@@ -39,8 +40,8 @@ constexpr int kNLAdjMinWaves = 5;
 // Indicator write mode of the adjoint kernels (the `has_eta` argument field):
 // bit 0 an indicator is wanted; bit 1 this launch assigns eta instead of adding to it (the
 // sweep's first launch under DG_ADJ_ETA_ASSIGN: no zero fill); bit 2 this launch stores
-// |eta| (the sweep's last launch under DG_ADJ_ETA_ABS).
-constexpr int kEtaOn = 1, kEtaAssign = 2, kEtaAbs = 4;
+// |eta| (the sweep's last launch under DG_ADJ_ETA_ABS).  kEtaOn, kEtaAssign, kEtaAbs and which
+// launch of a chain carries them: dg_chain.h.
 
 __device__ __forceinline__ void eta_update(double* __restrict__ eta, int64_t e, double acc,
                                            int mode) {
@@ -649,20 +650,24 @@ template <int NP> bool make_eo(const dg_plan* p, double scale, EOArgs<NP>* out, 
 
 inline unsigned grid_for(int64_t n, int64_t per) { return unsigned((n + per - 1) / per); }
 
-// Dispatch on Np (2..9) and the number of stages.
-#define DG_DISPATCH_NP(NPV, CALL) \
-  switch (NPV) {                  \
-    case 2: { constexpr int NP = 2; CALL; } break; \
-    case 3: { constexpr int NP = 3; CALL; } break; \
-    case 4: { constexpr int NP = 4; CALL; } break; \
-    case 5: { constexpr int NP = 5; CALL; } break; \
-    case 6: { constexpr int NP = 6; CALL; } break; \
-    case 7: { constexpr int NP = 7; CALL; } break; \
-    case 8: { constexpr int NP = 8; CALL; } break; \
-    case 9: { constexpr int NP = 9; CALL; } break; \
-    default: return fail(DG_ERR_ARG, "unsupported Np"); \
+// Dispatch on Np = 2 .. MAXNP: f(std::integral_constant<int, NP>) -> int.  Only the orders of
+// the range are instantiated (pair tiles and the general kernels 9, wave tiles and the
+// p-estimate 8).
+template <int MAXNP = kMaxNP, class F> int dispatch_np(int np, F&& f) {
+  static_assert(MAXNP >= 2 && MAXNP <= kMaxNP, "Np range");
+  switch (np) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: if constexpr (MAXNP >= 3) return f(std::integral_constant<int, 3>{}); break;
+    case 4: if constexpr (MAXNP >= 4) return f(std::integral_constant<int, 4>{}); break;
+    case 5: if constexpr (MAXNP >= 5) return f(std::integral_constant<int, 5>{}); break;
+    case 6: if constexpr (MAXNP >= 6) return f(std::integral_constant<int, 6>{}); break;
+    case 7: if constexpr (MAXNP >= 7) return f(std::integral_constant<int, 7>{}); break;
+    case 8: if constexpr (MAXNP >= 8) return f(std::integral_constant<int, 8>{}); break;
+    case 9: if constexpr (MAXNP >= 9) return f(std::integral_constant<int, 9>{}); break;
+    default: break;
   }
-
+  return fail(DG_ERR_ARG, "unsupported Np (2 .. " + std::to_string(MAXNP) + ")");
+}
 // Nonlinear-flux / per-stage-limiter steppers (dg_burgers.hip), dispatched from the C ABI
 // when plan->nonlinear().
 int nl_rhs(const dg_plan* p, const double* u, double* rhs, double t, hipStream_t st);
@@ -671,6 +676,30 @@ int nl_fwd(dg_plan* p, double* u, double t0, double dt, int nsteps, double* snap
            uint16_t* decisions, hipStream_t st);
 int nl_adj(dg_plan* p, double* w, const double* snapshots, double t0, double dt, int nsteps,
            double src_coef, double* eta, int flags, const uint16_t* decisions, hipStream_t st);
+
+// out = w + c * u over n doubles (k_axpy_copy, dg_advec.hip): the adjoint chains' node-0 source
+// and hand-back.
+int axpy_copy(const double* w, const double* u, double c, double* out, int64_t n, hipStream_t st);
+
+// copy(dst, src) of one field on the stream, as the chains of dg_chain.h take it.
+inline auto field_copy(int64_t field, hipStream_t st) {
+  return [=](double* dst, const double* src) -> int {
+    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * field, hipMemcpyDeviceToDevice, st));
+    return DG_OK;
+  };
+}
+
+// The launch shape of the linear forward sweep: steps per launch (before the caps of the tile
+// shape), elements per lane of the wave tiles (0: stage-loop workgroup tiles), pair-tile
+// snapshots.  The plan's own (msteps, lane_elems, snap_pairs) for dg_lserk4_fwd;
+// dg_lserk4_sweep_p marches at {4, 0, 0}.
+struct FwdShape {
+  int msteps, lane_elems, snap_pairs;
+};
+// The snapshot march of the linear forward (dg_advec.hip): snapshots[0] = u, rows 1 .. nsteps,
+// u = u^nsteps; tn: the nsteps + 1 time levels.
+int fwd_march(const dg_plan* p, FwdShape s, double* u, const double* tn, double dt, int nsteps,
+              double* snapshots, hipStream_t st);
 
 // Wave-tile variants of the linear LSERK4 step kernels (dg_wave.hip), selected by
 // plan->lane_elems; `times` as for the workgroup-tile launchers.

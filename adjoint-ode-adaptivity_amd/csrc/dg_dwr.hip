@@ -1018,26 +1018,23 @@ inline int p_horner() {
 }
 
 // Shapes: 256-element tiles with 1, 2 or 4 steps per launch; 512-element tiles with 2, 4 or 8.
+template <int N> using ic = std::integral_constant<int, N>;
 template <int NPL>
 int launch_adj_p_t(const dg_plan* lo, const dg_plan* hi, const PrEO<NPL>& pr, int ms,
                    const double* win, double* wout, const double* snap, double* eta, int em,
                    const double* tn, double dt, hipStream_t st, bool term) {
+  auto launch = [&](auto w, auto m) -> int {
+    if (p_horner())
+      return launch_adj_ph_e<NPL, w, m>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
+    return launch_adj_p_e<NPL, w, m>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
+  };
   const bool w2 = lo->p_tile_width == 2;
-  if (p_horner()) {
-    if (w2 && ms == 8) return launch_adj_ph_e<NPL, 2, 8>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
-    if (w2 && ms == 4) return launch_adj_ph_e<NPL, 2, 4>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
-    if (w2 && ms == 2) return launch_adj_ph_e<NPL, 2, 2>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
-    if (ms == 4) return launch_adj_ph_e<NPL, 1, 4>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
-    if (ms == 2) return launch_adj_ph_e<NPL, 1, 2>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
-    if (ms == 1) return launch_adj_ph_e<NPL, 1, 1>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st, term);
-    return fail(DG_ERR_ARG, "p-estimate: unsupported steps per launch for this tile width");
-  }
-  if (w2 && ms == 8) return launch_adj_p_e<NPL, 2, 8>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
-  if (w2 && ms == 4) return launch_adj_p_e<NPL, 2, 4>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
-  if (w2 && ms == 2) return launch_adj_p_e<NPL, 2, 2>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
-  if (ms == 4) return launch_adj_p_e<NPL, 1, 4>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
-  if (ms == 2) return launch_adj_p_e<NPL, 1, 2>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
-  if (ms == 1) return launch_adj_p_e<NPL, 1, 1>(lo, hi, pr, win, wout, snap, eta, em, tn, dt, st);
+  if (w2 && ms == 8) return launch(ic<2>{}, ic<8>{});
+  if (w2 && ms == 4) return launch(ic<2>{}, ic<4>{});
+  if (w2 && ms == 2) return launch(ic<2>{}, ic<2>{});
+  if (ms == 4) return launch(ic<1>{}, ic<4>{});
+  if (ms == 2) return launch(ic<1>{}, ic<2>{});
+  if (ms == 1) return launch(ic<1>{}, ic<1>{});
   return fail(DG_ERR_ARG, "p-estimate: unsupported steps per launch for this tile width");
 }
 
@@ -1048,10 +1045,16 @@ inline int p_msteps(const dg_plan* p) {
   if (m == 8 && p->p_tile_width != 2) m = 4;
   return m;
 }
-inline int chunk_p(const dg_plan* p, int left) {
-  int m = p_msteps(p);
-  while (m > left) m >>= 1;
-  return m < 1 ? 1 : m;
+
+// f(integral_constant NPL, PrEO<NPL>) -> int with the even/odd blocks of the prolongation P
+// for the lo plan's order (Np <= 8).
+template <class F> int with_prolong(const dg_plan* lo, const double* P, F&& f) {
+  return dispatch_np<8>(lo->NP, [&](auto np) -> int {
+    PrEO<np> pr;
+    if (!make_prolong_eo<np>(P, &pr))
+      return fail(DG_ERR_ARG, "P does not commute with the node reversal (symmetric nodes)");
+    return f(np, pr);
+  });
 }
 
 // Both plans describe one mesh and one problem (the order-(N+1) plan is the estimate's).
@@ -1104,29 +1107,16 @@ int adjp_flow(dg_plan* lo, const dg_plan* hi, const double* P, double* w,
   if (const int rc = p_flow_bufs(lo, hi, 0x5a, m, W, nsteps, int64_t(nb) * nT, int64_t(nb) * nT_cap,
                                  nT, nT_cap, nb, w, eta != nullptr, idx, value, nonfinite, st, &b))
     return rc;
-  int rc = DG_OK;
-  switch (lo->NP) {
-#define DG_ADJPF_CASE(NPLV)                                                                  \
-    case NPLV: {                                                                             \
-      PrEO<NPLV> pr;                                                                         \
-      if (!make_prolong_eo<NPLV>(P, &pr))                                                    \
-        return fail(DG_ERR_ARG, "P does not commute with the node reversal (symmetric nodes)"); \
-      if (W == 2 && m == 8)                                                                  \
-        rc = launch_adjp_flow<NPLV, 2, 8>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, \
-                                          term, st);                                         \
-      else if (W == 2)                                                                       \
-        rc = launch_adjp_flow<NPLV, 2, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, \
-                                          term, st);                                         \
-      else                                                                                   \
-        rc = launch_adjp_flow<NPLV, 1, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, \
-                                          term, st);                                         \
-    } break;
-    DG_ADJPF_CASE(2) DG_ADJPF_CASE(3) DG_ADJPF_CASE(4) DG_ADJPF_CASE(5)
-    DG_ADJPF_CASE(6) DG_ADJPF_CASE(7) DG_ADJPF_CASE(8)
-#undef DG_ADJPF_CASE
-    default: return fail(DG_ERR_ARG, "the p-estimate supports N <= 7");
-  }
-  return rc;
+  return with_prolong(lo, P, [&](auto np, const auto& pr) -> int {
+    if (W == 2 && m == 8)
+      return launch_adjp_flow<np, 2, 8>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, term,
+                                        st);
+    if (W == 2)
+      return launch_adjp_flow<np, 2, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, term,
+                                        st);
+    return launch_adjp_flow<np, 1, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, term,
+                                      st);
+  });
 }
 
 // The whole sweep as one dataflow launch applies: the estimate's dataflow shape at 4-step
@@ -1192,24 +1182,11 @@ int psweep(dg_plan* lo, const dg_plan* hi, const double* P, double* snapshots, d
                                  2 * int64_t(nb) * nT_cap, nT, nT_cap, nb, w, eta != nullptr, idx,
                                  value, nonfinite, st, &b))
     return rc;
-  int rc = DG_OK;
-  switch (lo->NP) {
-#define DG_PSWEEP_CASE(NPLV)                                                                 \
-    case NPLV: {                                                                             \
-      PrEO<NPLV> pr;                                                                         \
-      if (!make_prolong_eo<NPLV>(P, &pr))                                                    \
-        return fail(DG_ERR_ARG, "P does not commute with the node reversal (symmetric nodes)"); \
-      if (W == 2)                                                                            \
-        rc = launch_psweep<NPLV, 2, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, st); \
-      else                                                                                   \
-        rc = launch_psweep<NPLV, 1, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, st); \
-    } break;
-    DG_PSWEEP_CASE(2) DG_PSWEEP_CASE(3) DG_PSWEEP_CASE(4) DG_PSWEEP_CASE(5)
-    DG_PSWEEP_CASE(6) DG_PSWEEP_CASE(7) DG_PSWEEP_CASE(8)
-#undef DG_PSWEEP_CASE
-    default: return fail(DG_ERR_ARG, "the p-estimate supports N <= 7");
-  }
-  return rc;
+  return with_prolong(lo, P, [&](auto np, const auto& pr) -> int {
+    if (W == 2)
+      return launch_psweep<np, 2, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, st);
+    return launch_psweep<np, 1, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, st);
+  });
 }
 
 int adj_p_impl(dg_plan* lo, dg_plan* hi, const double* P, double* w, const double* snapshots,
@@ -1240,50 +1217,27 @@ int adj_p_impl(dg_plan* lo, dg_plan* hi, const double* P, double* w, const doubl
       return rc;
     term = false;
   }
-  std::vector<double> tn(size_t(nsteps) + 1);  // time = time + dt, as the forward sweep
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
-  if (p_flow_shape(lo, nsteps)) {
-    const int mode = eta ? (kEtaOn | ((flags & DG_ADJ_ETA_ASSIGN) ? kEtaAssign : 0) |
-                            ((flags & DG_ADJ_ETA_ABS) ? kEtaAbs : 0))
-                         : 0;
-    return adjp_flow(lo, hi, P, w, snapshots, tn.data(), dt, nsteps, eta, mode, term, idx, value,
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
+  const bool assign = flags & DG_ADJ_ETA_ASSIGN, abs = flags & DG_ADJ_ETA_ABS;
+  if (p_flow_shape(lo, nsteps))
+    return adjp_flow(lo, hi, P, w, snapshots, tn.data(), dt, nsteps, eta,
+                     chain::eta_sweep_mode(eta != nullptr, assign, abs), term, idx, value,
                      nonfinite, st);
-  }
   if (nsteps > 0) {
-    int launches = 0;
-    for (int n = nsteps; n > 0; n -= chunk_p(lo, n)) ++launches;
-    int l = 0;
-    const double* in = w;
-    for (int n = nsteps; n > 0; ++l) {  // this launch covers steps n-m .. n-1
-      const int m = chunk_p(lo, n);
-      const int n0 = n - m;
-      double* out = (l == launches - 1 && launches > 1)
-                        ? w : ((l % 2 == 0) ? hi->d_scratch : hi->d_scratch2);
-      const int em = ((l == 0 && (flags & DG_ADJ_ETA_ASSIGN)) ? kEtaAssign : 0) |
-                     ((n0 == 0 && (flags & DG_ADJ_ETA_ABS)) ? kEtaAbs : 0);
-      const double* snap = snapshots + int64_t(n0) * field_lo;
-      int rc = DG_OK;
-      switch (lo->NP) {
-#define DG_ADJP_CASE(NPLV)                                                                  \
-        case NPLV: {                                                                        \
-          PrEO<NPLV> pr;                                                                    \
-          if (!make_prolong_eo<NPLV>(P, &pr))                                               \
-            return fail(DG_ERR_ARG, "P does not commute with the node reversal (symmetric nodes)"); \
-          rc = launch_adj_p_t<NPLV>(lo, hi, pr, m, in, out, snap, eta, em, &tn[n0], dt, st,  \
-                                    term && l == 0);                                        \
-        } break;
-        DG_ADJP_CASE(2) DG_ADJP_CASE(3) DG_ADJP_CASE(4) DG_ADJP_CASE(5)
-        DG_ADJP_CASE(6) DG_ADJP_CASE(7) DG_ADJP_CASE(8)
-#undef DG_ADJP_CASE
-        default: return fail(DG_ERR_ARG, "the p-estimate supports N <= 7");
-      }
-      if (rc) return rc;
-      in = out;
-      n = n0;
-    }
-    if (in != w)  // a one-launch sweep went through scratch
-      HIP_TRY(hipMemcpyAsync(w, in, sizeof(double) * field_hi, hipMemcpyDeviceToDevice, st));
+    // the chain runs on order-(N+1) fields: the hi plan's scratch
+    const int rc = with_prolong(lo, P, [&](auto np, const auto& pr) -> int {
+      const chain::Result r = chain::reverse(
+          nsteps, [m0 = p_msteps(lo)](int left) { return chain::halve(m0, left); }, w,
+          hi->d_scratch, hi->d_scratch2, assign, abs,
+          [&](int l, int n0, int m, const double* in, double* out, int em) {
+            return launch_adj_p_t<np>(lo, hi, pr, m, in, out, snapshots + int64_t(n0) * field_lo,
+                                      eta, em, &tn[n0], dt, st, term && l == 0);
+          });
+      if (r.rc) return r.rc;
+      if (r.buf != w) return field_copy(field_hi, st)(w, r.buf);  // one launch: through scratch
+      return DG_OK;
+    });
+    if (rc) return rc;
   }
   return idx ? dg_argmax_ex(lo, eta, lo->ktot, 1, idx, value, nonfinite, stream) : DG_OK;
 }
@@ -1301,23 +1255,12 @@ int dg_prolong(const dg_plan* lo, const dg_plan* hi, const double* P, const doub
                                {"u_hi", u_hi, sizeof(double) * size_t(hi->ktot) * size_t(hi->NP)}}))
     return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc = DG_OK;
-  switch (lo->NP) {
-#define DG_PROLONG_CASE(NPLV)                                                               \
-    case NPLV: {                                                                            \
-      PrEO<NPLV> pr;                                                                        \
-      if (!make_prolong_eo<NPLV>(P, &pr))                                                   \
-        return fail(DG_ERR_ARG, "P does not commute with the node reversal (symmetric nodes)"); \
-      hipLaunchKernelGGL((k_prolong<NPLV>), dim3(grid_for(lo->ktot, kBlock)), dim3(kBlock), 0, \
-                         st, u, u_hi, pr, lo->ktot);                                        \
-      HIP_TRY(hipGetLastError());                                                           \
-    } break;
-    DG_PROLONG_CASE(2) DG_PROLONG_CASE(3) DG_PROLONG_CASE(4) DG_PROLONG_CASE(5)
-    DG_PROLONG_CASE(6) DG_PROLONG_CASE(7) DG_PROLONG_CASE(8)
-#undef DG_PROLONG_CASE
-    default: return fail(DG_ERR_ARG, "the p-estimate supports N <= 7");
-  }
-  return rc;
+  return with_prolong(lo, P, [&](auto np, const auto& pr) -> int {
+    hipLaunchKernelGGL((k_prolong<np>), dim3(grid_for(lo->ktot, kBlock)), dim3(kBlock), 0, st, u,
+                       u_hi, pr, lo->ktot);
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 int dg_lserk4_adj_p(dg_plan* lo, dg_plan* hi, const double* P, double* w, const double* snapshots,
@@ -1384,29 +1327,20 @@ int dg_lserk4_sweep_p(dg_plan* lo, dg_plan* hi, const double* P, double* snapsho
            {"value", value, sizeof(double)},
            {"nonfinite_count", nonfinite_count, sizeof(int64_t)}}))
     return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
   if (!p_sweep_shape(lo, nsteps)) {
     // the launch chains: the snapshot forward in place from snapshot 0 -- on the stage-loop
     // workgroup tiles at 4 steps per launch, the dataflow launch's forward blocks, so that the
     // result does not depend on whether nsteps fits that launch -- then the estimate
-    const int ms = lo->msteps, sp = lo->snap_pairs, le = lo->lane_elems;
-    lo->msteps = 4;
-    lo->snap_pairs = 0;
-    lo->lane_elems = 0;
-    const int rf = dg_lserk4_fwd_ex(lo, snapshots, t0, dt, nsteps, snapshots, nullptr, stream);
-    lo->msteps = ms;
-    lo->snap_pairs = sp;
-    lo->lane_elems = le;
-    if (rf) return rf;
+    if (const int rf = fwd_march(lo, FwdShape{4, 0, 0}, snapshots, tn.data(), dt, nsteps,
+                                 snapshots, st))
+      return rf;
     return adj_p_impl(lo, hi, P, w, snapshots, t0, dt, nsteps, eta,
                       flags | DG_ADJ_P_TERMINAL_PROLONG, idx, value, nonfinite_count, stream);
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  std::vector<double> tn(size_t(nsteps) + 1);  // time = time + dt (One_code.mlx:139)
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
-  const int mode = eta ? (kEtaOn | ((flags & DG_ADJ_ETA_ASSIGN) ? kEtaAssign : 0) |
-                          ((flags & DG_ADJ_ETA_ABS) ? kEtaAbs : 0))
-                       : 0;
+  const int mode = chain::eta_sweep_mode(eta != nullptr, flags & DG_ADJ_ETA_ASSIGN,
+                                         flags & DG_ADJ_ETA_ABS);
   return psweep(lo, hi, P, snapshots, w, tn.data(), dt, nsteps, eta, mode, idx, value,
                 nonfinite_count, st);
 }

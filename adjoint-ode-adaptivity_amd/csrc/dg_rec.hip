@@ -127,24 +127,6 @@ int rp_snap_e(const dg_plan* p, const double* in, double* snap, const double* ti
   return DG_OK;
 }
 
-template <int NP>
-int rp_snap_np(const dg_plan* p, int ms, const double* in, double* snap, const double* times,
-               double dt, hipStream_t st) {
-  const bool w2 = p->tile_width == 2;
-  switch (ms) {
-    case 8: return w2 ? rp_snap_e<NP, 8, 8>(p, in, snap, times, dt, st)
-                      : rp_snap_e<NP, 4, 8>(p, in, snap, times, dt, st);
-    case 4: return w2 ? rp_snap_e<NP, 8, 4>(p, in, snap, times, dt, st)
-                      : rp_snap_e<NP, 4, 4>(p, in, snap, times, dt, st);
-    case 2: return w2 ? rp_snap_e<NP, 8, 2>(p, in, snap, times, dt, st)
-                      : rp_snap_e<NP, 4, 2>(p, in, snap, times, dt, st);
-    case 1: return w2 ? rp_snap_e<NP, 8, 1>(p, in, snap, times, dt, st)
-                      : rp_snap_e<NP, 4, 1>(p, in, snap, times, dt, st);
-    default: break;
-  }
-  return fail(DG_ERR_ARG, "pair snapshot forward: 1, 2, 4 or 8 steps per launch");
-}
-
 template <int NP, int NW, int E, int MS>
 int rp_step_e(const dg_plan* p, const double* in, double* rec, double* last, const double* times,
               double dt, hipStream_t st, int64_t n0, bool jend) {
@@ -191,53 +173,25 @@ int rp_adj_e(const dg_plan* p, const double* win, double* wout, const double* re
 // waves per SIMD) were measured slower in both directions (profiles/r03/waves/: adjoint
 // 180 -> 200-244 us per sweep, forward 157-166 -> 183-220 us): the per-stage barrier waits
 // for more waves.
-template <int NP, int NW>
-int rp_step_w(const dg_plan* p, int ms, const double* in, double* rec, double* last,
-              const double* times, double dt, hipStream_t st, int64_t n0, bool jend) {
+// f(integral_constant NW, integral_constant MS) -> int for a tile width (1 / 2) and the steps
+// per launch; REC: the record sweeps' shapes, else the snapshot forward's (1, 2, 4 or 8).
+template <int N> using ic = std::integral_constant<int, N>;
+template <int NW, bool REC, class F> int pair_steps(int ms, F&& f) {
   switch (ms) {
-    case 20: if constexpr (NW == 8) return rp_step_e<NP, NW, 2, 20>(p, in, rec, last, times, dt, st, n0, jend); break;
-    case 16: if constexpr (NW == 8) return rp_step_e<NP, NW, 2, 16>(p, in, rec, last, times, dt, st, n0, jend); break;
-    case 10: return rp_step_e<NP, NW, 2, 10>(p, in, rec, last, times, dt, st, n0, jend);
-    case 8: return rp_step_e<NP, NW, 2, 8>(p, in, rec, last, times, dt, st, n0, jend);
-    case 5: return rp_step_e<NP, NW, 2, 5>(p, in, rec, last, times, dt, st, n0, jend);
-    case 4: return rp_step_e<NP, NW, 2, 4>(p, in, rec, last, times, dt, st, n0, jend);
-    case 2: return rp_step_e<NP, NW, 2, 2>(p, in, rec, last, times, dt, st, n0, jend);
-    case 1: return rp_step_e<NP, NW, 2, 1>(p, in, rec, last, times, dt, st, n0, jend);
+    case 20: if constexpr (REC && NW == 8) return f(ic<NW>{}, ic<20>{}); break;
+    case 16: if constexpr (REC && NW == 8) return f(ic<NW>{}, ic<16>{}); break;
+    case 10: if constexpr (REC) return f(ic<NW>{}, ic<10>{}); break;
+    case 8: return f(ic<NW>{}, ic<8>{});
+    case 5: if constexpr (REC) return f(ic<NW>{}, ic<5>{}); break;
+    case 4: return f(ic<NW>{}, ic<4>{});
+    case 2: return f(ic<NW>{}, ic<2>{});
+    case 1: return f(ic<NW>{}, ic<1>{});
     default: break;
   }
   return fail(DG_ERR_ARG, "pair tiles: unsupported steps per launch for this tile width");
 }
-
-template <int NP, int NW>
-int rp_adj_w(const dg_plan* p, int ms, const double* win, double* wout, const double* rec,
-             double* eta, int em, const double* t_next, double dt, hipStream_t st, int64_t n0) {
-  switch (ms) {
-    case 20: if constexpr (NW == 8) return rp_adj_e<NP, NW, 2, 20>(p, win, wout, rec, eta, em, t_next, dt, st, n0); break;
-    case 16: if constexpr (NW == 8) return rp_adj_e<NP, NW, 2, 16>(p, win, wout, rec, eta, em, t_next, dt, st, n0); break;
-    case 10: return rp_adj_e<NP, NW, 2, 10>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 8: return rp_adj_e<NP, NW, 2, 8>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 5: return rp_adj_e<NP, NW, 2, 5>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 4: return rp_adj_e<NP, NW, 2, 4>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 2: return rp_adj_e<NP, NW, 2, 2>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 1: return rp_adj_e<NP, NW, 2, 1>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
-    default: break;
-  }
-  return fail(DG_ERR_ARG, "pair tiles: unsupported steps per launch for this tile width");
-}
-
-template <int NP>
-int rp_step_np(const dg_plan* p, int ms, const double* in, double* rec, double* last,
-               const double* times, double dt, hipStream_t st, int64_t n0, bool jend) {
-  if (rec_fwd_width(p) == 2) return rp_step_w<NP, 8>(p, ms, in, rec, last, times, dt, st, n0, jend);
-  return rp_step_w<NP, 4>(p, ms, in, rec, last, times, dt, st, n0, jend);
-}
-
-template <int NP>
-int rp_adj_np(const dg_plan* p, int ms, const double* win, double* wout, const double* rec,
-              double* eta, int em, const double* t_next, double dt, hipStream_t st, int64_t n0) {
-  if (p->rec_tile_width == 2)
-    return rp_adj_w<NP, 8>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-  return rp_adj_w<NP, 4>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
+template <bool REC, class F> int pair_shape(int width, int ms, F&& f) {
+  return width == 2 ? pair_steps<8, REC>(ms, f) : pair_steps<4, REC>(ms, f);
 }
 
 }  // namespace
@@ -246,48 +200,30 @@ namespace dgk {
 
 int pair_launch_step_rec(const dg_plan* p, int ms, const double* in, double* rec, double* last,
                          const double* times, double dt, hipStream_t st, int64_t n0, bool jend) {
-  switch (p->NP) {
-    case 2: return rp_step_np<2>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 3: return rp_step_np<3>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 4: return rp_step_np<4>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 5: return rp_step_np<5>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 6: return rp_step_np<6>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 7: return rp_step_np<7>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 8: return rp_step_np<8>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    case 9: return rp_step_np<9>(p, ms, in, rec, last, times, dt, st, n0, jend);
-    default: return fail(DG_ERR_ARG, "pair tiles support Np <= 9");
-  }
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    return pair_shape<true>(rec_fwd_width(p), ms, [&](auto nw, auto m) -> int {
+      return rp_step_e<np, nw, 2, m>(p, in, rec, last, times, dt, st, n0, jend);
+    });
+  });
 }
 
 int pair_launch_step_snap(const dg_plan* p, int ms, const double* in, double* snap,
                           const double* times, double dt, hipStream_t st) {
-  switch (p->NP) {
-    case 2: return rp_snap_np<2>(p, ms, in, snap, times, dt, st);
-    case 3: return rp_snap_np<3>(p, ms, in, snap, times, dt, st);
-    case 4: return rp_snap_np<4>(p, ms, in, snap, times, dt, st);
-    case 5: return rp_snap_np<5>(p, ms, in, snap, times, dt, st);
-    case 6: return rp_snap_np<6>(p, ms, in, snap, times, dt, st);
-    case 7: return rp_snap_np<7>(p, ms, in, snap, times, dt, st);
-    case 8: return rp_snap_np<8>(p, ms, in, snap, times, dt, st);
-    case 9: return rp_snap_np<9>(p, ms, in, snap, times, dt, st);
-    default: return fail(DG_ERR_ARG, "pair tiles support Np <= 9");
-  }
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    return pair_shape<false>(p->tile_width, ms, [&](auto nw, auto m) -> int {
+      return rp_snap_e<np, nw, m>(p, in, snap, times, dt, st);
+    });
+  });
 }
 
 int pair_launch_adj_rec(const dg_plan* p, int ms, const double* win, double* wout,
                         const double* rec, double* eta, int em, const double* t_next, double dt,
                         hipStream_t st, int64_t n0) {
-  switch (p->NP) {
-    case 2: return rp_adj_np<2>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 3: return rp_adj_np<3>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 4: return rp_adj_np<4>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 5: return rp_adj_np<5>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 6: return rp_adj_np<6>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 7: return rp_adj_np<7>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 8: return rp_adj_np<8>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    case 9: return rp_adj_np<9>(p, ms, win, wout, rec, eta, em, t_next, dt, st, n0);
-    default: return fail(DG_ERR_ARG, "pair tiles support Np <= 9");
-  }
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    return pair_shape<true>(p->rec_tile_width, ms, [&](auto nw, auto m) -> int {
+      return rp_adj_e<np, nw, 2, m>(p, win, wout, rec, eta, em, t_next, dt, st, n0);
+    });
+  });
 }
 
 }  // namespace dgk

@@ -285,9 +285,7 @@ int sweep_launch(dg_plan* p, const dgk::SweepBufs& b, double t0, double dt, int 
   SweepArgs<NP, MSF> a;
   if (const int rc = rp_make_op<NP>(p, dt, &a.c)) return rc;
   const int nbF = nsteps / MSF, nbA = nsteps / MSA;
-  std::vector<double> tn(size_t(nsteps) + 1);  // time = time + dt (One_code.mlx:139)
-  tn[0] = t0;
-  for (int n = 0; n < nsteps; ++n) tn[n + 1] = tn[n] + dt;
+  const std::vector<double> tn = dgk::chain::time_levels(t0, dt, nsteps);
   for (int bk = 0; bk < nbF; ++bk)
     rp_block_bnd(p, MSF, &tn[size_t(bk) * MSF], dt, a.bnd + bk * (MSF * 6 + 1));
   for (int i = 0; i <= kSweepMaxBlocks; ++i) {

@@ -270,11 +270,12 @@ int dg_time_march(int Np, int nq, const double* S, const double* Phi, const doub
   if (lds > 64 * 1024) return fail(DG_ERR_ARG, "operators exceed 64 KiB of LDS");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for(n_ics, kTimeBlock);
-  DG_DISPATCH_NP(Np, hipLaunchKernelGGL((k_dgt_march<NP>), dim3(grid), dim3(kTimeBlock), lds, st,
-                                        S, Phi, wq, nq, times, n_slabs, y0, n_ics, tol, maxit, Y,
-                                        iters));
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return dispatch_np(Np, [&](auto np) -> int {
+    hipLaunchKernelGGL((k_dgt_march<np>), dim3(grid), dim3(kTimeBlock), lds, st, S, Phi, wq, nq,
+                       times, n_slabs, y0, n_ics, tol, maxit, Y, iters);
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
+  });
 }
 
 int dg_time_adjoint(int Np_fwd, int nq, const double* Sa, const double* Ma, const double* Phia,

@@ -254,7 +254,8 @@ int transfer(const dg_plan* p, const int32_t* parent, int64_t k_old, const doubl
                                {"in", in, TO ? n_old : n_new}, {"out", out, TO ? n_new : n_old}}))
     return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  DG_DISPATCH_NP(p->NP, {
+  return dispatch_np(p->NP, [&](auto np) -> int {
+    constexpr int NP = np;
     TransferArgs<NP> a;
     for (int i = 0; i < NP * NP; ++i) a.A[i] = A[i];
     a.total = p->ktot;
@@ -270,9 +271,9 @@ int transfer(const dg_plan* p, const int32_t* parent, int64_t k_old, const doubl
     else
       hipLaunchKernelGGL((k_from_children<NP>), dim3(grid_for(p->ktot, kBlock)), dim3(kBlock),
                          0, st, in, out, parent, a);
+    HIP_TRY(hipGetLastError());
+    return DG_OK;
   });
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
 }
 
 }  // namespace

@@ -239,28 +239,22 @@ int launch_wstep_e(const dg_plan* p, const double* in, double* snap, double* las
   return DG_OK;
 }
 
-template <int NP>
-int wstep_np(const dg_plan* p, int ms, const double* in, double* snap, double* last,
-             const double* times, double dt, hipStream_t st) {
-  if (p->lane_elems == 8) {
-    if (ms == 8) return launch_wstep_e<NP, 8, 8>(p, in, snap, last, times, dt, st);
-    if (ms == 4) return launch_wstep_e<NP, 8, 4>(p, in, snap, last, times, dt, st);
-    if (ms == 2) return launch_wstep_e<NP, 8, 2>(p, in, snap, last, times, dt, st);
-    return launch_wstep_e<NP, 8, 1>(p, in, snap, last, times, dt, st);
+// Shapes: E = 2, 4 or 8 elements per lane x 1, 2, 4 or 8 steps per launch; no 8 steps at
+// E = 2 (a 128-element tile leaves no room for the 8-step cone; effective_msteps caps these
+// plans at 4).
+template <int NP, int E>
+int wstep_e(const dg_plan* p, int ms, const double* in, double* snap, double* last,
+            const double* times, double dt, hipStream_t st) {
+  switch (ms) {
+    case 8:
+      if constexpr (E > 2) return launch_wstep_e<NP, E, 8>(p, in, snap, last, times, dt, st);
+      break;
+    case 4: return launch_wstep_e<NP, E, 4>(p, in, snap, last, times, dt, st);
+    case 2: return launch_wstep_e<NP, E, 2>(p, in, snap, last, times, dt, st);
+    case 1: return launch_wstep_e<NP, E, 1>(p, in, snap, last, times, dt, st);
+    default: break;
   }
-  if (p->lane_elems == 4) {
-    if (ms == 8) return launch_wstep_e<NP, 4, 8>(p, in, snap, last, times, dt, st);
-    if (ms == 4) return launch_wstep_e<NP, 4, 4>(p, in, snap, last, times, dt, st);
-    if (ms == 2) return launch_wstep_e<NP, 4, 2>(p, in, snap, last, times, dt, st);
-    if (ms == 1) return launch_wstep_e<NP, 4, 1>(p, in, snap, last, times, dt, st);
-    return fail(DG_ERR_ARG, "wave tiles: unsupported steps per launch");
-  }
-  // 2 elements per lane: a 128-element tile leaves no room for the 8-step cone
-  // (effective_msteps caps these plans at 4)
-  if (ms == 4) return launch_wstep_e<NP, 2, 4>(p, in, snap, last, times, dt, st);
-  if (ms == 2) return launch_wstep_e<NP, 2, 2>(p, in, snap, last, times, dt, st);
-  if (ms == 1) return launch_wstep_e<NP, 2, 1>(p, in, snap, last, times, dt, st);
-  return fail(DG_ERR_ARG, "wave tiles of 2 elements per lane take at most 4 steps per launch");
+  return fail(DG_ERR_ARG, "wave tiles: unsupported steps per launch for this tile");
 }
 
 }  // namespace
@@ -269,18 +263,11 @@ namespace dgk {
 
 int wave_launch_step(const dg_plan* p, int ms, const double* in, double* snap, double* last,
                      const double* times, double dt, hipStream_t st) {
-  int rc = DG_OK;
-  switch (p->NP) {
-    case 2: rc = wstep_np<2>(p, ms, in, snap, last, times, dt, st); break;
-    case 3: rc = wstep_np<3>(p, ms, in, snap, last, times, dt, st); break;
-    case 4: rc = wstep_np<4>(p, ms, in, snap, last, times, dt, st); break;
-    case 5: rc = wstep_np<5>(p, ms, in, snap, last, times, dt, st); break;
-    case 6: rc = wstep_np<6>(p, ms, in, snap, last, times, dt, st); break;
-    case 7: rc = wstep_np<7>(p, ms, in, snap, last, times, dt, st); break;
-    case 8: rc = wstep_np<8>(p, ms, in, snap, last, times, dt, st); break;
-    default: return fail(DG_ERR_ARG, "wave tiles support Np <= 8");
-  }
-  return rc;
+  return dispatch_np<8>(p->NP, [&](auto np) -> int {
+    if (p->lane_elems == 8) return wstep_e<np, 8>(p, ms, in, snap, last, times, dt, st);
+    if (p->lane_elems == 4) return wstep_e<np, 4>(p, ms, in, snap, last, times, dt, st);
+    return wstep_e<np, 2>(p, ms, in, snap, last, times, dt, st);
+  });
 }
 
 }  // namespace dgk

@@ -34,7 +34,7 @@ def geometry_fail(what):
 
 
 def grid_for(n, per):
-  return (n + per - 1) // per  # csrc/dg_common.h:615
+  return (n + per - 1) // per  # csrc/dg_common.h:651
 
 
 # --- owned extents (TE, H) per family, from the plan ----------------------------------
@@ -78,8 +78,8 @@ def snap_pair_extents(op):
 
 def record_extents(op):
   """forward_rec / adjoint_rec.  Pair tiles (2 elements per lane): T = 512 * width, forward
-  H = RpHalo<MSF>::F on the forward's width, adjoint H = RpHalo<MSA>::A (csrc/dg_rec.hip:156,
-  :175).  One element per lane: the stage-loop record kernels; only the forward takes the
+  H = RpHalo<MSF>::F on the forward's width, adjoint H = RpHalo<MSA>::A (csrc/dg_rec.hip:138,
+  :157).  One element per lane: the stage-loop record kernels; only the forward takes the
   record's extra element, H = 5*MS + 1 (csrc/dg_advec.hip:761, csrc/dg_step_tile.h:67), the
   adjoint keeps H = 5*MS with the record too (csrc/dg_advec.hip:790, adj_tile :92-93)."""
   w, msa, lanes, msf = _q(op, "dg_plan_query_rec", 4)
@@ -99,7 +99,7 @@ def sweep_query(op, nsteps):
 def sweep_extents(op, nsteps):
   """The dataflow launch: both directions on tiles of T elements (128 * waves, 256 * waves
   with 4 elements per lane, 116 * waves + 12 on overlapped waves, csrc/dg_ovl_tiles.h:40), TEF
-  = T - 2*RpHalo<MSF>::F, TEA = T - 2*RpHalo<MSA>::A (csrc/dg_sweep_kernel.h:107-108, :311)."""
+  = T - 2*RpHalo<MSF>::F, TEA = T - 2*RpHalo<MSA>::A (csrc/dg_sweep_kernel.h:107-108, :309)."""
   on, msf, msa, _, _, T = sweep_query(op, nsteps)
   assert on, "this shape does not run as the dataflow launch"
   return [(T - 2 * halo_f(msf), halo_f(msf)), (T - 2 * halo_a(msa), halo_a(msa))]
@@ -117,7 +117,7 @@ def check_sweep_items(op, nsteps, ext):
 
 def p_extents(op):
   """adjp / adjp_flow / psweep on tiles of 256*W lanes, one element per lane: H = 5*MS
-  (csrc/dg_dwr.hip:394, :484, :1100; the psweep's blocks are 4 steps, :1187)."""
+  (csrc/dg_dwr.hip:394, :484, :1103; the psweep's blocks are 4 steps, :1177)."""
   W, MS = _q(op, "dg_plan_query_p", 2)
   return [(256 * W - 10 * MS, 5 * MS)]
 
@@ -160,7 +160,7 @@ def source_constant(name, file, pattern=None):
 
 def limiter_extents():
   """k_limit (slope_limit, slope_limit_1): tiles of kBlock lanes with H = 1, TE = kBlock - 2
-  (csrc/dg_advec.hip:407-408; launches grid_for(ktot, kBlock - 2), :1974, :1985)."""
+  (csrc/dg_advec.hip:407-408; launches grid_for(ktot, kBlock - 2), :1928, :1942)."""
   H = source_constant("k_limit H", "dg_advec.hip",
                       r"constexpr int H = (\d+);\s*constexpr int TE = kBlock - 2 \* H;")
   return [(source_constant("kBlock", "dg_common.h") - 2 * H, H)]
@@ -168,14 +168,14 @@ def limiter_extents():
 
 def nl_extents(op, snapshots, known):
   """Config 3.  Forward: workgroup tiles of 256*kNLStepW = 512 elements, H = MS*5*cone (cone =
-  cone_per_stage<LIM> = 2 with a limiter, csrc/dg_burgers.hip:398), or with nl_exchange = 1 (one
+  cone_per_stage<LIM> = 2 with a limiter, csrc/dg_burgers.hip:391), or with nl_exchange = 1 (one
   step per launch) 4 windows of S = 64 - 2*G owned elements, G = 5*cone, TE = kOwWaves * S
   (csrc/dg_burgers_ov.hip:47-51, :345).  Adjoint: 256*kNLAdjW = 256-element tiles with H = 10
-  with the decision record and 10*cone without (csrc/dg_burgers.hip:418; k_adj_nl works on
+  with the decision record and 10*cone without (csrc/dg_burgers.hip:411; k_adj_nl works on
   half tiles TH = TE/2, :290), or on overlapped waves (record or no limiter) G = kOwAdjG = 10:
   TE = 4 * 44 (csrc/dg_burgers_ov.hip:214, :363).  The constants are read from csrc/
   (``source_constant``): no query reports them.  With ``snapshots`` a third entry gives the
-  forward without snapshots where its steps per launch differ (csrc/dg_burgers.hip:500-503)."""
+  forward without snapshots where its steps per launch differ (csrc/dg_burgers.hip:493-496)."""
   ex, ms_snap, ms_plain = _q(op, "dg_plan_query_nl", 3)
   kBlock = source_constant("kBlock", "dg_common.h")
   step_w = source_constant("kNLStepW", "dg_burgers.hip")
