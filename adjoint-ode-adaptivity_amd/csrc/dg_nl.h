@@ -658,13 +658,18 @@ template <int NP> LimEO<NP> make_lim_eo(const dg_plan* p) {
   }
   const double V00 = p->V[0];  // V(1,1): the cell average is V(1,1) uh(1)
   for (int k = 0; k < NE; ++k) c.a0e[k] *= V00;
-  double d0 = 0.0, d1 = 0.0;
+  // (Dr V)(1,1:2), summed in long double (host only).  d0 is the derivative of a constant: zero
+  // but for rounding, and an fp64 sum leaves it at its own summation noise (N^2 eps: 9e-16 at
+  // N = 4), which dv0 then multiplies into the cell average: a spurious slope on every branch-1
+  // cell, 7e-15 (N = 4) to 3e-14 (N = 7) of max|u| after 4 steps against 1e-15 with the sum
+  // rounded once (tests/test_gpu_extended_limiter.py).
+  long double d0 = 0.0L, d1 = 0.0L;
   for (int l = 0; l < NP; ++l) {
-    d0 += p->Dr[l] * p->V[l * NP + 0];
-    d1 += p->Dr[l] * p->V[l * NP + 1];
+    d0 += static_cast<long double>(p->Dr[l]) * p->V[l * NP + 0];
+    d1 += static_cast<long double>(p->Dr[l]) * p->V[l * NP + 1];
   }
-  c.dv0 = 2.0 * d0 / V00;  // uh(1) = avg / V(1,1)
-  c.dv1 = 2.0 * d1;
+  c.dv0 = static_cast<double>(2.0L * d0 / V00);  // uh(1) = avg / V(1,1)
+  c.dv1 = static_cast<double>(2.0L * d1);
   c.every = p->limiter == DG_LIMIT_PI1_EACH_STAGE;
   return c;
 }

@@ -1,6 +1,6 @@
-"""Helpers of tests/test_oracle_extended.py (CPU) and tests/test_gpu_extended.py: the cases of
-the extended-precision anchor, their inputs built on the host, and per case the
-oracle in long double (oracle/extended.py) next to the fp64 numpy oracle on the same inputs,
+"""Helpers of tests/test_oracle_extended.py (CPU), tests/test_gpu_extended.py and
+tests/test_gpu_extended_limiter.py: the cases of the extended-precision anchor,
+their inputs built on the host, and per case the oracle in long double (oracle/extended.py) next to the fp64 numpy oracle on the same inputs,
 cached per case key and read-only.
 
 For a quantity q: qX the long-double result, e64(q) = max|q64 - qX| / max|qX| the fp64 numpy
@@ -52,18 +52,23 @@ class Report:
   def __init__(self, case_id):
     self.case_id, self.rows = case_id, []
 
-  def add(self, what, got, x, d, margin=MARGIN):
-    """``got`` the GPU's, ``x`` the long-double and ``d`` the fp64 oracle's value."""
+  def add(self, what, got, x, d, margin=MARGIN, cap=CAP):
+    """``got`` the GPU's, ``x`` the long-double and ``d`` the fp64 oracle's value; ``cap``: the
+    family's reference-alone condition where it is not CAP (k_limit's derived one)."""
     e64, eg = err(d, x), err(got, x)
-    self.rows.append((what, eg, e64, margin))
+    self.rows.append((what, eg, e64, margin, cap))
     print(f"  {self.case_id} {what}: eg = {eg:.3e}  e64 = {e64:.3e}  "
           f"eg/max(e64, FLOOR) = {eg / max(e64, FLOOR):.2f}")
 
   def check(self):
-    for what, eg, e64, margin in self.rows:
-      assert e64 <= CAP, (self.case_id, what, "the reference alone exceeds CAP", e64)
-    for what, eg, e64, margin in self.rows:
+    for what, eg, e64, margin, cap in self.rows:
+      assert e64 <= cap, (self.case_id, what, "the reference alone exceeds its condition", e64)
+    for what, eg, e64, margin, cap in self.rows:
       assert eg <= margin * max(e64, FLOOR), (self.case_id, what, eg, e64)
+
+  def worst(self):
+    """(eg / max(e64, FLOOR), what, eg, e64) of the row nearest its bound."""
+    return max((eg / max(e64, FLOOR), what, eg, e64) for what, eg, e64, _, _ in self.rows)
 
 
 # --- the tile extents, by formula (checked against the plan in the GPU tests) ------------------
@@ -406,3 +411,210 @@ def transfer_ld(u, parent, k_old, A, to_children, batch=1):
       elif role[n] == 1:
         out[b, parent[n]] = A @ u[b, n] + AR @ u[b, n + 1]
   return out.ravel()
+
+
+# --- the limited paths (families 12, 13; DESIGN.md §3 "The limiter paths") ------------------------
+GAP = 1e-11  # condition (b): every decision margin of a case, in units of max|u|
+SHARE = 0.005  # condition (d): each code class's least share of all decisions, per limiter kind
+# 2*TE + 1 of the record-driven adjoint's extent per nl_exchange (tests/tile_edges.nl_extents with
+# a limiter): workgroup tiles TE = 256 - 2*10, overlapped waves TE = 4 * (64 - 2*10); and of the
+# snapshot forward on workgroup tiles, TE = 512 - 2*10 (one step per launch, two cells per stage)
+LIM_K = {0: 2 * 236 + 1, 1: 2 * 176 + 1}
+LIM_K_FWD = 2 * 492 + 1
+# quiet cases: 3*TE + 1, so that an interior tile's halo ends before the last element (the ends of
+# a trajectory are always troubled: the replicated neighbour zeroes the minmod)
+LIM_K_QUIET = {0: 3 * 236 + 1, 1: 3 * 176 + 1}
+LIM_UNIT = {0: 236, 1: 44}  # the record-driven adjoint's unit: a tile / an overlapped-wave window
+PHYSICS = {"BN": ("burgers", "N"), "B1": ("burgers", "1"), "LN": ("linear", "N")}
+
+
+def _lim_cases():
+  """(physics, exchange, N, uniform, point, src, seed, shape, own pipeline).  ``shape``: "adj"
+  K of the adjoint's extent, "fwd" of the forward's, "quiet" noise and jump only on the first
+  elements.  Meshes alternate so that every (physics, exchange) has both kinds."""
+  out = []
+  for ip, ph in enumerate(PHYSICS):
+    for ex in (0, 1):
+      for iN, N in enumerate((1, 2, 4, 7)):
+        i = len(out)
+        out.append((ph, ex, N, (iN + ex + ip) % 2 == 0, "HOME", 0.3 * (i % 2), 0, "adj",
+                    N == 2 and ex == ip % 2))
+  out.append(("BN", 0, 2, False, "AWAY", 0.3, 0, "adj", False))
+  out.append(("BN", 0, 2, True, "HOME", 0.0, 0, "quiet", False))
+  out.append(("LN", 1, 4, False, "HOME", 0.3, 0, "quiet", False))
+  out.append(("B1", 0, 1, False, "HOME", 0.0, 0, "fwd", False))
+  out.append(("BN", 0, 2, True, "HOME", 0.3, 0, "fwd", False))
+  return out
+
+
+LIM_CASES = _lim_cases()
+POINTS = dict(HOME=HOME, AWAY=AWAY)
+
+
+def lim_id(c):
+  ph, ex, N, uni, point, src, seed, shape, own = c
+  return f"{ph}-x{ex}-N{N}-{'uni' if uni else 'ref'}-{point}-src{src:g}-s{seed}-{shape}"
+
+
+def lim_k(c):
+  ex, shape = c[1], c[7]
+  return {"adj": LIM_K[ex], "fwd": LIM_K_FWD, "quiet": LIM_K_QUIET[ex]}[shape]
+
+
+def refined_vx(K, seed, x0=0.0, x1=1.0):
+  """tests/test_gpu_nonlinear.refined_vx (7 random bisections of a uniform mesh) with K elements
+  in all, on [x0, x1]."""
+  rng = np.random.default_rng(seed)
+  v = setup1d.mesh_gen1d(0.0, 1.0, K - 7)[1]
+  for _ in range(7):
+    j = int(rng.integers(0, len(v) - 1))
+    v = np.insert(v, j + 1, 0.5 * (v[j] + v[j + 1]))
+  return v if (x0, x1) == (0.0, 1.0) else x0 + (x1 - x0) * v
+
+
+def lim_mesh(pkg, c):
+  N, uni, p, K = c[2], c[3], POINTS[c[4]], lim_k(c)
+  v_x = setup1d.mesh_gen1d(p["x0"], p["x1"], K)[1] if uni else \
+      refined_vx(K, 100 * N + K, p["x0"], p["x1"])
+  return pkg.BaseGalerkin1D(n=N, v_x=v_x), v_x
+
+
+def lim_setups(mesh, v_x):
+  """(S64, SX) with every operator the plan is created with: Dr, LIFT, V, invV and r."""
+  S = ox.with_operators(setup1d.startup1d(mesh.n, v_x, metric="element"), mesh.d_r, mesh.lift,
+                        mesh.v, mesh.inv_v, mesh.r_gl)
+  return S, ox.widen(S)
+
+
+def lim_u0(c, S):
+  """A smooth sine + a jump + N(0, 0.05^2) nodal noise (tests/test_gpu_nonlinear.ic on the
+  case's domain).  "quiet": a monotone sine arc, the jump and the noise on the first 3/4 of a
+  unit only, so that whole tiles (windows) with their halos have no troubled cell."""
+  ph, ex, N, uni, point, src, seed, shape, own = c
+  p = POINTS[point]
+  rng = np.random.default_rng(1000 * seed + 10 * N + ex + len(ph) + S["K"])
+  xi = (S["x"] - p["x0"]) / (p["x1"] - p["x0"])
+  z = rng.standard_normal(xi.shape)
+  if shape == "quiet":
+    k = np.arange(S["K"])[None, :]
+    rough = k < 3 * LIM_UNIT[ex] // 4
+    return np.sin(0.3 + xi) + np.where(rough, 0.8 * (k > LIM_UNIT[ex] // 3) + 0.05 * z, 0.0)
+  return np.sin(TWO_PI * xi) + 0.8 * (xi > 0.5) + 0.05 * z
+
+
+def lim_weight(c, S):
+  """The adjoint's terminal weight: N(0,1) nodal noise.  The weight u^N is piecewise linear after
+  the limiter and excites only two functionals per cell of the transposed limiter (sum_i w_i and
+  sum_i r_i w_i); noise excites every node, so every coefficient of a0e / a1o / rco shows."""
+  rng = np.random.default_rng(77 + 1000 * c[6] + 10 * c[2] + c[1] + S["K"])
+  return rng.standard_normal(S["x"].shape)
+
+
+def lim_forward_ref(pkg, c):
+  """Both runs of oracle/extended.py's limited sweep from the case's u^0 (``X`` long double,
+  ``D`` the same code in fp64), with codes and margins."""
+  def make():
+    ph, ex, N, uni, point, src, seed, shape, own = c
+    flux, limit = PHYSICS[ph]
+    p = POINTS[point]
+    mesh, v_x = lim_mesh(pkg, c)
+    S, SX = lim_setups(mesh, v_x)
+    dt = te.bench_dt(N, v_x, p["a"])
+    u0 = lim_u0(c, S)
+    g = lim_weight(c, S)
+    sx, times, cx, mx = ox.lim_forward_sweep(ox.field(u0), p["t0"], dt, NL_STEPS, p["a"], SX, flux,
+                                             p["inflow"], limit)
+    sd, _, cd, md = ox.lim_forward_sweep(u0, p["t0"], dt, NL_STEPS, p["a"], S, flux, p["inflow"],
+                                         limit)
+    assert sd[-1].dtype == np.float64 and sx[-1].dtype == LD
+    return dict(mesh=mesh, v_x=v_x, S=S, SX=SX, u0=em(u0), g=em(g), dt=dt, times=times, flux=flux,
+                limit=limit, point=p, _sx=sx, _sd=sd,
+                X=freeze(dict(snaps=[em(s) for s in sx], codes=cx, margin=mx)),
+                D=freeze(dict(snaps=[em(s) for s in sd], codes=cd, margin=md)))
+  return cached(("lim", c), make)
+
+
+def lim_adjoint_on(ref, snaps_em, src):
+  """Both runs' w^0, eta, recomputed codes and margin fed the same fp64 snapshots, terminal
+  weight ``ref["g"]``."""
+  N = ref["mesh"].n
+  sd = [setup1d.from_elem_major(s, N + 1) for s in snaps_em]
+  sx = [ox.field(s) for s in sd]
+  p, dt, t = ref["point"], ref["dt"], ref["times"]
+  args = (ref["flux"], p["inflow"], ref["limit"], src)
+  g = setup1d.from_elem_major(ref["g"], N + 1)
+  wx, ex, cx, mx = ox.lim_adjoint_sweep(ox.field(g), sx, t, dt, p["a"], ref["SX"], *args)
+  wd, ed, cd, md = ox.lim_adjoint_sweep(g, sd, t, dt, p["a"], ref["S"], *args)
+  return dict(X=dict(w0=em(wx), eta=ex, codes=cx, margin=mx),
+              D=dict(w0=em(wd), eta=ed, codes=cd, margin=md))
+
+
+def lim_adjoint_own(pkg, c):
+  """Each run's adjoint on its OWN forward states (the CPU module's e64 of w^0 and eta, and the
+  reference of the self-contained pipelines)."""
+  ref = lim_forward_ref(pkg, c)
+
+  def make():
+    p, dt, t = ref["point"], ref["dt"], ref["times"]
+    args = (ref["flux"], p["inflow"], ref["limit"], c[5])
+    sx, sd = ref["_sx"], ref["_sd"]
+    g = setup1d.from_elem_major(ref["g"], ref["mesh"].n + 1)
+    wx, ex, cx, mx = ox.lim_adjoint_sweep(ox.field(g), sx, t, dt, p["a"], ref["SX"], *args)
+    wd, ed, cd, md = ox.lim_adjoint_sweep(g, sd, t, dt, p["a"], ref["S"], *args)
+    return freeze(dict(X=dict(w0=em(wx), eta=ex, codes=cx, margin=mx),
+                       D=dict(w0=em(wd), eta=ed, codes=cd, margin=md)))
+  return cached(("lim-adj", c), make)
+
+
+def class_counts(codes, limit):
+  """Decisions per code class (0, 4, 5, 6, 7) of a (..., K) code array."""
+  return {k: int(np.count_nonzero(codes == k)) for k in ((4, 5, 6, 7) if limit == "1" else (0, 4, 5, 6, 7))}
+
+
+def quiet_units(words, unit, halo=10):
+  """Per step of a (nsteps, K) record, which adjoint units (tiles, windows) have a troubled cell
+  within their halo (tests/test_gpu_decisions.test_troubled_tiles_on_the_wide_cone)."""
+  nsteps, K = words.shape
+  n = -(-K // unit)
+  out = np.zeros((nsteps, n), dtype=bool)
+  for t in range(n):
+    out[:, t] = words[:, max(t * unit - halo, 0):t * unit + unit + halo].any(axis=1)
+  return out
+
+
+# k_limit (family 13): (N, uniform, kind, M)
+KLIMIT_K = 2 * 254 + 1
+KLIMIT = [(1, True, "N", None), (4, False, "N", None), (7, True, "N", None),
+          (1, False, "1", None), (4, True, "1", None), (7, False, "1", None),
+          (4, False, "N", "tvb")]
+
+
+def klimit_ref(pkg, i):
+  """The stand-alone limiters: long-double truth (mesh-free form, coordinates from the widened VX
+  and r), the restatement in fp64 (codes, margin), and oracle/limiter.py's coordinate form in
+  fp64, which shares k_limit's cancellation and is the ``e64`` of this family."""
+  from oracle import limiter as olim
+
+  def make():
+    N, uni, kind, M = KLIMIT[i]
+    c = ("BN", 0, N, uni, "HOME", 0.0, 3, "adj", False)
+    v_x = setup1d.mesh_gen1d(0.0, 1.0, KLIMIT_K)[1] if uni else refined_vx(KLIMIT_K, 7 + N)
+    mesh = pkg.BaseGalerkin1D(n=N, v_x=v_x)
+    S, SX = lim_setups(mesh, v_x)
+    u = lim_u0(c, S)
+    h = np.diff(v_x)
+    if M == "tvb":  # between the two middle values of |ux| / h^2 over the troubled cells: both
+      # sides of |ux| > M h^2 occur, and no cell sits on the threshold
+      q = np.sort((np.abs(ox._slope_arg(u, S)) / h ** 3)[ox.slope_limit(u, S, kind)[1] != 0])
+      M = float(np.sqrt(q[len(q) // 2 - 1] * q[len(q) // 2]))
+    yx, cx, mx = ox.slope_limit(ox.field(u), SX, kind, M)
+    yd, cd, md = ox.slope_limit(u, S, kind, M)
+    if kind == "1":
+      y64, ids = olim.slope_limit_1(u, S, M), np.arange(S["K"])
+    else:
+      y64, ids = olim.slope_limit_n(u, S, return_ids=True, M=M)
+    cond = 1e-14 + 4 * 2.0 ** -52 * float(np.max(np.abs(v_x)) / np.min(h))
+    return freeze(dict(mesh=mesh, v_x=v_x, S=S, SX=SX, u=em(u), M=M, kind=kind, cond=cond,
+                       X=dict(y=em(yx), codes=cx, margin=mx), D=dict(y=em(yd), codes=cd, margin=md),
+                       C=dict(y=em(y64), ids=np.sort(ids))))
+  return cached(("klimit", i), make)
