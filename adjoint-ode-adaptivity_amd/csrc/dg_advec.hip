@@ -855,48 +855,6 @@ int launch_adj(const dg_plan* p, int ms, const double* win, double* wout, const 
   });
 }
 
-// Record sweeps run on pair tiles (dg_rec.hip), Np <= 9, unless DG_TUNE_REC_LANE_ELEMENTS = 1
-// selects the one-element-per-lane record kernels below: W = 1 with 1..4 steps, W = 2 with
-// 1..8; Np = 9: at most 2 steps there (1024-element one-element-per-lane tiles -- 16-wave
-// workgroups, 74 KB of LDS -- measured 20 % slower).
-inline bool rec_pairs(const dg_plan* p) { return p->rec_lane_elems == 2; }
-
-// Record steps per launch: pair tiles take 1, 2, 4, 5, 8, 10, 16 or 20 (a sweep is chunked by
-// halving: 20 -> 10 -> 5 -> 2 -> 1); the one-element-per-lane kernels 1, 2, 4 or 8.
-inline bool rec_msteps_ok(int k) {
-  return k == 1 || k == 2 || k == 4 || k == 5 || k == 8 || k == 10 || k == 16 || k == 20;
-}
-
-// The record steps per launch the plan's shape allows for a requested value m on tiles of
-// width w.
-inline int rec_msteps_cap(const dg_plan* p, int m, int w) {
-  if (!rec_pairs(p)) {
-    int q = 1;
-    while (q * 2 <= m && q < 8) q *= 2;
-    m = q;
-  }
-  if (m == 8 && w == 1 && !rec_pairs(p)) m = 4;
-  if (rec_pairs(p) && w == 1 && m > 10) m = (m == 16) ? 8 : 10;
-  if (!rec_pairs(p) && p->NP > 8 && m > 2) m = 2;
-  return m;
-}
-
-// Adjoint (and, unless overridden, forward) record steps per launch.
-inline int rec_msteps(const dg_plan* p) { return rec_msteps_cap(p, p->rec_msteps, p->rec_tile_width); }
-
-// Forward record steps per launch.  By size (the default): one 20-step launch on 1024-element
-// pair tiles while a 10-step launch would be only ~1.5-4 rounds of workgroups (up to 3*2^20
-// elements: at K = 2^20 / 2^21 the forward is 5 / 2 % faster than 10 + 10), beyond that the
-// adjoint's setting (at 2^22 equal, at config 4's 67 M elements 10 + 10 is 3 % faster: the
-// wider halo outweighs the launch saved).  The adjoint prefers 10 + 10 at every size.
-inline int rec_msteps_fwd(const dg_plan* p) {
-  int m = p->rec_msteps_fwd;
-  if (m < 0)
-    m = (rec_pairs(p) && rec_fwd_width(p) == 2 && p->ktot <= (int64_t(3) << 20)) ? 20
-                                                                             : p->rec_msteps;
-  return rec_msteps_cap(p, m ? m : p->rec_msteps, rec_fwd_width(p));
-}
-
 // Jump-record launches: on pair tiles, or LSERK4 (NS = 5) on the workgroup tiles at the
 // record's tile width and steps per launch.
 int launch_step_rec(const dg_plan* p, int ms, const double* in, double* rec, double* last,
@@ -920,18 +878,6 @@ int launch_adj_rec(const dg_plan* p, int ms, const double* win, double* wout, co
   });
 }
 
-// Steps per launch the plan's shape allows: 8 only with 512-element tiles (the cone is
-// 8*NS elements per side) and Np <= 8; at Np = 9 at most 2 (hipcc/ROCm 7.2 fails
-// instruction selection for the 4-step shape there).
-inline int effective_msteps(const dg_plan* p, FwdShape s) {
-  int m = s.msteps;
-  if (m == 8 && !(p->tile_width == 2 || s.lane_elems == 8)) m = 4;
-  if (m == 8 && s.lane_elems == 2) m = 4;  // 128-element wave tiles: cone too wide
-  if (p->NP > 8 && m > 2) m = 2;
-  return m;
-}
-inline FwdShape plan_shape(const dg_plan* p) { return {p->msteps, p->lane_elems, p->snap_pairs}; }
-
 // The chunk functions (dg_chain.h) of the linear sweeps, halving the plan's setting: the
 // snapshot sweeps' ({8, 4, 2, 1}) and the jump-record sweeps' (20 -> 10 -> 5 -> 2 -> 1).
 inline auto chunk(const dg_plan* p, FwdShape s) {
@@ -941,60 +887,6 @@ inline auto chunk_rec(const dg_plan* p, bool fwd) {
   return [m0 = fwd ? rec_msteps_fwd(p) : rec_msteps(p)](int left) { return chain::halve(m0, left); };
 }
 
-// The dataflow sweep's blocks for `nsteps` steps (dg_sweep.hip): true with the forward /
-// adjoint steps per block when the plan runs it -- pair tiles of one width in both
-// directions (1024 or 512 elements), the record shape's 5-, 10- or 20-step (1024 only)
-// forward and 5- or 10-step adjoint launches as its blocks, nsteps a multiple of both and at
-// most sweep_max_steps() -- else false (the launch-per-block pair runs, same results).
-// With the plan's sweep_waves set (DG_TUNE_SWEEP_WAVES) the dataflow launch runs both
-// directions on tiles of 128 * sweep_waves elements, whatever the launch chains' widths: 12
-// and 16 waves take the 10- or 20-step forward and 10-step adjoint blocks (16 at Np <= 5).
-// Unset (0), the shape follows the record sweeps' tile width, with the measured exceptions
-// below (12-wave tiles at Np <= 5, 8-wave tiles at Np = 9 on uniform meshes).
-bool sweep_shape(const dg_plan* p, int nsteps, int* waves, int* msf, int* msa) {
-  const int f = rec_msteps_fwd(p), a = rec_msteps(p), w = p->rec_tile_width;
-  const int sw = p->sweep_waves;
-  int nw = sw;
-  bool tiles;
-  if (sw) {
-    tiles = (sw == 4 || sw == 8) || ((sw == 12 || (sw == 16 && p->NP <= 5)) && f >= 10 && a == 10);
-  } else if (p->NP == 9 && p->uniform) {
-    // the launch chains run 1024-element forward and 512-element adjoint tiles here; the one
-    // launch takes 8-wave (1024-element) tiles in both directions: 7.06-7.23e11 DOF-updates/s
-    // at K = 2^20 against 6.65e11 for the chains (profiles/r04/opreload/)
-    nw = 8;
-    tiles = true;
-  } else {
-    // as the record sweeps' tile width; on the 6-wave-per-SIMD uniform bodies (Np <= 5) 12-wave
-    // tiles where their shape allows (1536 elements, 2 workgroups per CU; forward halo 1.15
-    // instead of 1.25, a third fewer items): +3-4 % at N = 4, +1-3 % at N = 2
-    // (profiles/r04/take/, perN/, shape_ab/)
-    nw = 4 * w;
-    tiles = rec_fwd_width(p) == w && (w == 1 || w == 2);
-    // (Np = 2 keeps 8 waves: at 8 waves per SIMD, four 8-wave groups per CU, see SweepOcc)
-    if (tiles && w == 2 && p->uniform && p->NP >= 3 && p->NP <= 5 && p->sweep_lane_elems == 2 &&
-        f >= 10 && a == 10)
-      nw = 12;
-  }
-  *msf = f;
-  *msa = a;
-  *waves = nw;
-  tiles = tiles && (p->sweep_lane_elems == 2 || (p->NP <= 3 && (nw == 4 || nw == 8)));
-  if (p->sweep_exchange == 1)  // overlapped waves: pairs on 8, 12 or 16 (Np <= 5) waves, 20- or
-                               // 10-step forward and 10-step adjoint blocks
-    tiles = tiles && p->sweep_lane_elems == 2 &&
-            (nw == 8 || nw == 12 || (nw == 16 && p->NP <= 5)) && f >= 10 && a == 10;
-  const int T = sweep_tile_elems(p, nw);  // elements per tile
-  return p->rec_sweep && rec_pairs(p) && tiles &&
-         (f == 5 || f == 10 || (f == 20 && T >= 900)) && (a == 5 || a == 10) && nsteps > 0 &&
-         nsteps % f == 0 && nsteps % a == 0 && nsteps <= sweep_max_steps();
-}
-
-// The plan's dataflow scratch: a control region of sync words and flags (zeroed once, then
-// kept consistent by the kernel's epochs) followed by a data region (block states, indicator
-// partials).  Grows the control region to `sync_bytes` (zeroing what it newly covers, which
-// an earlier call may have used as data) and the allocation to hold `data_bytes` after it.
-// *data = the data region's start.
 }  // namespace
 
 namespace dgk {
@@ -1106,6 +998,11 @@ int dg_plan_create(int N, int64_t K, int64_t batch, const double* r, const doubl
   p->inflow = inflow_variant;
   p->scheme = time_scheme;
   p->nstages = (time_scheme == DG_TIME_LSERK4) ? 5 : 1;
+  // the one failure exit: the plan goes, with whatever it holds so far
+  auto bail = [&](int code, const std::string& m) {
+    dg_plan_destroy(p);
+    return fail(code, m);
+  };
   const int NP = p->NP;
   std::memcpy(p->r, r, sizeof(double) * NP);
   std::memcpy(p->V, V, sizeof(double) * NP * NP);
@@ -1117,23 +1014,16 @@ int dg_plan_create(int N, int64_t K, int64_t batch, const double* r, const doubl
   if (const int rc = dispatch_np(p->NP, [&](auto np) -> int {
         sym = make_eo<np>(p, 1.0, nullptr);
         return DG_OK;
-      })) {
-    delete p;
-    return rc;
-  }
-  if (!sym) {
-    delete p;
-    return fail(DG_ERR_ARG, "Dr/LIFT are not centro-(anti)symmetric (nodes must be symmetric)");
-  }
+      }))
+    return bail(rc, std::string(dg_last_error()));
+  if (!sym)
+    return bail(DG_ERR_ARG, "Dr/LIFT are not centro-(anti)symmetric (nodes must be symmetric)");
 
   std::vector<double> scale(K);
   double hmin = 1e300, hmax = -1e300, hsum = 0.0;
   for (int64_t k = 0; k < K; ++k) {
     const double h = VX[k + 1] - VX[k];
-    if (!(h > 0.0)) {
-      delete p;
-      return fail(DG_ERR_ARG, "VX must be strictly increasing");
-    }
+    if (!(h > 0.0)) return bail(DG_ERR_ARG, "VX must be strictly increasing");
     scale[k] = 2.0 / h;
     hmin = h < hmin ? h : hmin;
     hmax = h > hmax ? h : hmax;
@@ -1164,92 +1054,9 @@ int dg_plan_create(int N, int64_t K, int64_t batch, const double* r, const doubl
   // launch (k_adjp_flow) on 512-element tiles with 4-step blocks: 410 us per 20-step estimate
   // at N = 4, K = 2^20 against 437 for the launch chain of direct-to-LDS 256-element tiles and
   // 443 for the chain with register prefetch (profiles/r05/p13; the chain drains each launch:
-  // 4,855 tiles are 3.16 rounds of the 1,536 resident workgroups).
-  p->p_tile_width = 2;
-  p->p_flow = 1;
-  p->p_sweep = 1;
-  {
-    if (const char* v = std::getenv("DG_TILE_WIDTH")) {
-      const int k = std::atoi(v);
-      if (k == 1 || k == 2) p->tile_width = k;
-    }
-    if (const char* v = std::getenv("DG_LANE_ELEMENTS")) {
-      const int k = std::atoi(v);
-      if (k == 0 || k == 2 || k == 4 || k == 8) p->lane_elems = k;
-    }
-    if (const char* v = std::getenv("DG_STEPS_PER_LAUNCH")) {
-      const int k = std::atoi(v);
-      if (k == 1 || k == 2 || k == 4 || k == 8) p->msteps = k;
-    }
-    if (const char* v = std::getenv("DG_REC_TILE_WIDTH")) {
-      const int k = std::atoi(v);
-      if (k == 1 || k == 2) {
-        p->rec_tile_width = k;
-        p->rec_tile_width_fwd = 0;  // both directions, as DG_TUNE_REC_TILE_WIDTH
-      }
-    }
-    if (const char* v = std::getenv("DG_REC_FWD_TILE_WIDTH")) {
-      const int k = std::atoi(v);
-      if (k == 0 || k == 1 || k == 2) p->rec_tile_width_fwd = k;
-    }
-    if (const char* v = std::getenv("DG_REC_STEPS_PER_LAUNCH")) {
-      const int k = std::atoi(v);
-      // both directions, as DG_TUNE_REC_STEPS_PER_LAUNCH (the forward's own override below)
-      if (rec_msteps_ok(k)) {
-        p->rec_msteps = k;
-        p->rec_msteps_fwd = 0;
-      }
-    }
-    if (const char* v = std::getenv("DG_REC_FWD_STEPS_PER_LAUNCH")) {
-      const int k = std::atoi(v);
-      if (rec_msteps_ok(k)) p->rec_msteps_fwd = k;
-    }
-    if (const char* v = std::getenv("DG_REC_LANE_ELEMENTS")) {
-      const int k = std::atoi(v);
-      if (k == 1 || k == 2) p->rec_lane_elems = k;
-    }
-    if (const char* v = std::getenv("DG_P_TILE_WIDTH")) {
-      const int k = std::atoi(v);
-      if (k == 1 || k == 2) p->p_tile_width = k;
-    }
-    if (const char* v = std::getenv("DG_P_STEPS_PER_LAUNCH")) {
-      const int k = std::atoi(v);
-      if (k == 1 || k == 2 || k == 4 || k == 8) p->p_msteps = k;
-    }
-  if (const char* v = std::getenv("DG_P_FLOW")) {
-    const int k = std::atoi(v);
-    if (k == 0 || k == 1) p->p_flow = k;
-  }
-  if (const char* v = std::getenv("DG_P_SWEEP")) {
-    const int k = std::atoi(v);
-    if (k == 0 || k == 1) p->p_sweep = k;
-  }
-  }
-  if (const char* v = std::getenv("DG_REC_SWEEP")) {
-    const int k = std::atoi(v);
-    if (k == 0 || k == 1) p->rec_sweep = k;
-  }
-  if (const char* v = std::getenv("DG_SWEEP_LANE_ELEMENTS")) {
-    const int k = std::atoi(v);
-    if (k == 2 || (k == 4 && p->NP <= 3)) p->sweep_lane_elems = k;
-  }
-  if (const char* v = std::getenv("DG_SNAP_PAIRS")) {
-    const int k = std::atoi(v);
-    if (k == 0 || k == 1) p->snap_pairs = k;
-  }
-  if (const char* v = std::getenv("DG_SWEEP_EXCHANGE")) {
-    const int k = std::atoi(v);
-    if (k == 0 || k == 1) p->sweep_exchange = k;
-  }
-  if (const char* v = std::getenv("DG_NL_EXCHANGE")) {
-    const int e = std::atoi(v);
-    if (e == 0 || e == 1) p->nl_exchange = e;
-  }
-  if (const char* v = std::getenv("DG_SWEEP_WAVES")) {
-    const int k = std::atoi(v);
-    if (k == 0 || k == 4 || k == 8 || k == 12 || (k == 16 && p->NP <= 5)) p->sweep_waves = k;
-  }
-
+  // 4,855 tiles are 3.16 rounds of the 1,536 resident workgroups): Shape's defaults.
+  // The environment overrides, after the per-N defaults.
+  tune::from_env(p, [](const char* name) { return std::getenv(name); });
   {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -1257,24 +1064,23 @@ int dg_plan_create(int N, int64_t K, int64_t batch, const double* r, const doubl
       p->cu_count = cus;
     if (p->cu_count < 1) p->cu_count = 1;
   }
-  auto cleanup = [&](const std::string& m) {
-    dg_plan_destroy(p);
-    return fail(DG_ERR_NOMEM, m);
-  };
-  if (hipMalloc(&p->d_scale, sizeof(double) * K) != hipSuccess) return cleanup("hipMalloc scale");
-  if (hipMalloc(&p->d_VX, sizeof(double) * (K + 1)) != hipSuccess) return cleanup("hipMalloc VX");
+  if (hipMalloc(&p->d_scale, sizeof(double) * K) != hipSuccess)
+    return bail(DG_ERR_NOMEM, "hipMalloc scale");
+  if (hipMalloc(&p->d_VX, sizeof(double) * (K + 1)) != hipSuccess)
+    return bail(DG_ERR_NOMEM, "hipMalloc VX");
   if (hipMalloc(&p->d_scratch, sizeof(double) * p->ktot * NP) != hipSuccess)
-    return cleanup("hipMalloc scratch");
+    return bail(DG_ERR_NOMEM, "hipMalloc scratch");
   if (hipMalloc(&p->d_scratch2, sizeof(double) * p->ktot * NP) != hipSuccess)
-    return cleanup("hipMalloc scratch2");
-  if (hipMalloc(&p->d_pv, sizeof(double) * kArgmaxParts) != hipSuccess) return cleanup("hipMalloc pv");
-  if (hipMalloc(&p->d_pi, sizeof(int64_t) * kArgmaxParts) != hipSuccess) return cleanup("hipMalloc pi");
-  if (hipMalloc(&p->d_mark, kMarkBytes) != hipSuccess) return cleanup("hipMalloc mark");
+    return bail(DG_ERR_NOMEM, "hipMalloc scratch2");
+  if (hipMalloc(&p->d_pv, sizeof(double) * kArgmaxParts) != hipSuccess)
+    return bail(DG_ERR_NOMEM, "hipMalloc pv");
+  if (hipMalloc(&p->d_pi, sizeof(int64_t) * kArgmaxParts) != hipSuccess)
+    return bail(DG_ERR_NOMEM, "hipMalloc pi");
+  if (hipMalloc(&p->d_mark, kMarkBytes) != hipSuccess)
+    return bail(DG_ERR_NOMEM, "hipMalloc mark");
   if (hipMemcpy(p->d_scale, scale.data(), sizeof(double) * K, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(p->d_VX, VX, sizeof(double) * (K + 1), hipMemcpyHostToDevice) != hipSuccess) {
-    dg_plan_destroy(p);
-    return fail(DG_ERR_HIP, "hipMemcpy of mesh failed");
-  }
+      hipMemcpy(p->d_VX, VX, sizeof(double) * (K + 1), hipMemcpyHostToDevice) != hipSuccess)
+    return bail(DG_ERR_HIP, "hipMemcpy of mesh failed");
   *out = p;
   return DG_OK;
 }
@@ -1335,118 +1141,15 @@ int dg_plan_query_nl(const dg_plan* p, int64_t out[3]) {
 int dg_plan_query_p(const dg_plan* p, int64_t out[2]) {
   if (!p || !out) return fail(DG_ERR_ARG, "null argument");
   out[0] = p->p_tile_width;
-  out[1] = (p->p_msteps == 8 && p->p_tile_width != 2) ? 4 : p->p_msteps;
+  out[1] = p_msteps(p);
   return DG_OK;
 }
 
 int dg_plan_tune(dg_plan* p, int key, int64_t value) {
   if (!p) return fail(DG_ERR_ARG, "null plan");
-  switch (key) {
-    case DG_TUNE_P_TILE_WIDTH:
-      if (value != 1 && value != 2) return fail(DG_ERR_ARG, "p-estimate tile width must be 1 or 2");
-      p->p_tile_width = int(value);
-      return DG_OK;
-    case DG_TUNE_P_STEPS_PER_LAUNCH:
-      if (value != 1 && value != 2 && value != 4 && value != 8)
-        return fail(DG_ERR_ARG, "p-estimate steps per launch must be 1, 2, 4 or 8");
-      p->p_msteps = int(value);
-      return DG_OK;
-    case DG_TUNE_REC_TILE_WIDTH:
-      if (value != 1 && value != 2)
-        return fail(DG_ERR_ARG, "record tile width must be 1 or 2");
-      p->rec_tile_width = int(value);
-      p->rec_tile_width_fwd = 0;  // both directions
-      return DG_OK;
-    case DG_TUNE_REC_FWD_TILE_WIDTH:
-      if (value != 0 && value != 1 && value != 2)
-        return fail(DG_ERR_ARG, "forward record tile width must be 0 (as the adjoint's), 1 or 2");
-      p->rec_tile_width_fwd = int(value);
-      return DG_OK;
-    case DG_TUNE_REC_STEPS_PER_LAUNCH:
-      if (!rec_msteps_ok(int(value)))
-        return fail(DG_ERR_ARG, "record steps per launch must be 1, 2, 4, 5, 8, 10, 16 or 20");
-      p->rec_msteps = int(value);
-      p->rec_msteps_fwd = 0;  // both directions
-      return DG_OK;
-    case DG_TUNE_REC_FWD_STEPS_PER_LAUNCH:
-      if (!rec_msteps_ok(int(value)))
-        return fail(DG_ERR_ARG, "record steps per launch must be 1, 2, 4, 5, 8, 10, 16 or 20");
-      p->rec_msteps_fwd = int(value);
-      return DG_OK;
-    case DG_TUNE_REC_LANE_ELEMENTS:
-      if (value != 1 && value != 2)
-        return fail(DG_ERR_ARG, "record lane elements must be 1 or 2");
-      p->rec_lane_elems = int(value);
-      return DG_OK;
-    case DG_TUNE_SWEEP_WAVES:
-      if (!(value == 0 || value == 4 || value == 8 || value == 12 || (value == 16 && p->NP <= 5)))
-        return fail(DG_ERR_ARG, "sweep waves: 0 (as the record tile width), 4, 8, 12 or 16 "
-                                "(16 at Np <= 5)");
-      p->sweep_waves = int(value);
-      return DG_OK;
-    case DG_TUNE_SWEEP_LANE_ELEMENTS:
-      if (!(value == 2 || (value == 4 && p->NP <= 3)))
-        return fail(DG_ERR_ARG, "sweep lane elements: 2, or 4 at Np <= 3");
-      p->sweep_lane_elems = int(value);
-      return DG_OK;
-    case DG_TUNE_SWEEP_TAKE:
-      // removed in round 5 (item = workgroup id relied on in-order dispatch per XCD): only the
-      // take counter (0) remains
-      if (value != 0) return fail(DG_ERR_ARG, "sweep take: only 0 (the take counter) is supported");
-      return DG_OK;
-    case DG_TUNE_P_SWEEP:
-      if (value != 0 && value != 1)
-        return fail(DG_ERR_ARG, "p sweep: 0 (the chains) or 1 (one dataflow launch)");
-      p->p_sweep = int(value);
-      return DG_OK;
-    case DG_TUNE_P_FLOW:
-      if (value != 0 && value != 1)
-        return fail(DG_ERR_ARG, "p-estimate flow: 0 (one launch per block) or 1 (one dataflow launch)");
-      p->p_flow = int(value);
-      return DG_OK;
-    case DG_TUNE_SNAP_PAIRS:
-      if (value != 0 && value != 1)
-        return fail(DG_ERR_ARG, "snapshot pairs: 0 (stage-loop kernels) or 1 (Horner pair tiles)");
-      p->snap_pairs = int(value);
-      return DG_OK;
-    case DG_TUNE_SWEEP_EXCHANGE:
-      if (value != 0 && value != 1)
-        return fail(DG_ERR_ARG, "sweep exchange: 0 (LDS + barrier per level) or 1 (overlapped waves)");
-      p->sweep_exchange = int(value);
-      return DG_OK;
-    case DG_TUNE_NL_EXCHANGE:
-      if (value != 0 && value != 1)
-        return fail(DG_ERR_ARG, "config-3 exchange: 0 (workgroup tiles, LDS) or 1 (overlapped waves)");
-      p->nl_exchange = int(value);
-      return DG_OK;
-    case DG_TUNE_SWEEP_SPIN_LIMIT:
-      if (value < 0 || value > (1 << 30)) return fail(DG_ERR_ARG, "spin limit: 0 (default) .. 2^30");
-      p->sweep_spin_limit = int(value);
-      return DG_OK;
-    case DG_TUNE_REC_SWEEP:
-      if (value != 0 && value != 1) return fail(DG_ERR_ARG, "record sweep mode must be 0 or 1");
-      p->rec_sweep = int(value);
-      return DG_OK;
-    case DG_TUNE_TILE_WIDTH:
-      if (value != 1 && value != 2) return fail(DG_ERR_ARG, "tile width must be 1 or 2");
-      p->tile_width = int(value);
-      return DG_OK;
-    case DG_TUNE_XCD_ORDER:
-      p->xcd_order = value ? 1 : 0;
-      return DG_OK;
-    case DG_TUNE_LANE_ELEMENTS:
-      if (value != 0 && value != 2 && value != 4 && value != 8)
-        return fail(DG_ERR_ARG, "lane elements must be 0, 2, 4 or 8");
-      p->lane_elems = int(value);
-      return DG_OK;
-    case DG_TUNE_STEPS_PER_LAUNCH:
-      if (value != 1 && value != 2 && value != 4 && value != 8)
-        return fail(DG_ERR_ARG, "steps per launch must be 1, 2, 4 or 8");
-      p->msteps = int(value);
-      return DG_OK;
-    default:
-      return fail(DG_ERR_ARG, "unknown tuning key");
-  }
+  const char* why = "";
+  const int rc = tune::set(p, key, value, &why);
+  return rc ? fail(rc, why) : DG_OK;
 }
 
 int dg_plan_set_tvb(dg_plan* p, double M) {
@@ -1747,8 +1450,8 @@ int sweep_rec_impl(dg_plan* p, const double* u0, double* uN, double* w, double* 
                                {"idx", idx, sizeof(int64_t)}, {"value", value, sizeof(double)},
                                {"nonfinite_count", nonfinite, sizeof(int64_t)}}))
     return rc;
-  int waves = 0, msf = 0, msa = 0;
-  if (!sweep_shape(p, nsteps, &waves, &msf, &msa)) {
+  const auto [on, waves, msf, msa] = sweep_shape(p, nsteps);
+  if (!on) {
     // the launch-per-block pair: forward into uN (or w when it is the terminal weight, or a
     // scratch field), then the adjoint in place on w
     double* fin = uN;
@@ -1831,6 +1534,22 @@ int sweep_rec_impl(dg_plan* p, const double* u0, double* uN, double* w, double* 
                                          aflags & DG_ADJ_ETA_ABS);
   return sweep_launch_rec(p, waves, msf, msa, b, t0, dt, nsteps, mode, st);
 }
+
+// The dg_plan_query_sweep* family: the null check and the resolved shape; out[0..3] = {on,
+// forward steps per block, adjoint steps per block, work items}.
+struct SweepQuery {
+  int rc;
+  SweepShape s;
+};
+SweepQuery query_sweep(const dg_plan* p, int nsteps, int64_t* out) {
+  if (!p || !out) return {fail(DG_ERR_ARG, "null argument"), {}};
+  const SweepShape s = sweep_shape(p, nsteps);
+  out[0] = s.on ? 1 : 0;
+  out[1] = s.msf;
+  out[2] = s.msa;
+  out[3] = s.on ? sweep_items(p, s.waves, s.msf, s.msa, nsteps) : 0;
+  return {DG_OK, s};
+}
 }  // namespace
 
 extern "C" {
@@ -1852,14 +1571,7 @@ int dg_lserk4_sweep_refine(dg_plan* p, const double* u0, double* uN, double* w, 
 }
 
 int dg_plan_query_sweep(const dg_plan* p, int nsteps, int64_t out[4]) {
-  if (!p || !out) return fail(DG_ERR_ARG, "null argument");
-  int waves = 0, msf = 0, msa = 0;
-  const bool on = sweep_shape(p, nsteps, &waves, &msf, &msa);
-  out[0] = on ? 1 : 0;
-  out[1] = msf;
-  out[2] = msa;
-  out[3] = on ? sweep_items(p, waves, msf, msa, nsteps) : 0;
-  return DG_OK;
+  return query_sweep(p, nsteps, out).rc;
 }
 
 int dg_plan_sweep_trace(dg_plan* p, uint64_t* trace) {
@@ -1869,32 +1581,26 @@ int dg_plan_sweep_trace(dg_plan* p, uint64_t* trace) {
 }
 
 int dg_plan_query_sweep_ex(const dg_plan* p, int nsteps, int64_t out[6]) {
-  if (!p || !out) return fail(DG_ERR_ARG, "null argument");
-  int waves = 0, msf = 0, msa = 0;
-  const bool on = sweep_shape(p, nsteps, &waves, &msf, &msa);
-  out[0] = on ? 1 : 0;
-  out[1] = msf;
-  out[2] = msa;
-  out[3] = on ? sweep_items(p, waves, msf, msa, nsteps) : 0;
-  out[4] = waves;
-  out[5] = sweep_tile_elems(p, waves);
+  const SweepQuery q = query_sweep(p, nsteps, out);
+  if (q.rc) return q.rc;
+  out[4] = q.s.waves;
+  out[5] = sweep_tile_elems(p, q.s.waves);
   return DG_OK;
 }
 
 int dg_plan_query_sweep_kernel(const dg_plan* p, int nsteps, int64_t out[8]) {
-  if (!p || !out) return fail(DG_ERR_ARG, "null argument");
-  int waves = 0, msf = 0, msa = 0;
-  const bool on = sweep_shape(p, nsteps, &waves, &msf, &msa);
+  const SweepQuery q = query_sweep(p, nsteps, out);
+  if (q.rc) return q.rc;
   for (int i = 0; i < 8; ++i) out[i] = 0;
-  if (!on) return DG_OK;
+  if (!q.s.on) return DG_OK;
   out[0] = p->NP;
   out[1] = p->uniform ? 1 : 0;
-  out[2] = waves;
-  out[3] = msf;
-  out[4] = msa;
+  out[2] = q.s.waves;
+  out[3] = q.s.msf;
+  out[4] = q.s.msa;
   out[5] = p->sweep_lane_elems;
   out[6] = p->sweep_exchange;
-  out[7] = sweep_waves_per_simd(p, waves);
+  out[7] = sweep_waves_per_simd(p, q.s.waves);
   return DG_OK;
 }
 

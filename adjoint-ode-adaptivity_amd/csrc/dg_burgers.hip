@@ -483,16 +483,9 @@ int launch_nl_step(const dg_plan* p, int ms, const double* in, double* snap, dou
   });
 }
 
-// Steps per limited-forward launch: 1 or 2 (the cone is 10 elements per step).  The
-// workgroup-tile kernels are barrier-bound, so the 2-step cone's extra halo (20 instead of
-// 10 elements per 256-element tile) costs more than the HBM round trip it saves whenever the
-// snapshots are written anyway: the default (msteps 4) runs 1 step per launch with snapshots
-// and 2 without (A/B at K = 2^22: 82 against 88 µs per step with snapshots, 84 against 80.5
-// without).  An explicit msteps of 1 or 2 is kept.  The overlapped waves run 1 step per
-// launch (a 2-step window would own 24 of its 64 elements).
+// The limited forward's chunk function: nl_msteps (dg_shape.h) steps per launch.
 inline auto chunk_nl(const dg_plan* p, bool snapshots) {
-  const int m = (p->msteps == 2 || (p->msteps > 2 && !snapshots && !p->nl_exchange)) ? 2 : 1;
-  return [m](int left) { return m > left ? left : m; };
+  return [m = nl_msteps(p, snapshots)](int left) { return m > left ? left : m; };
 }
 
 }  // namespace
@@ -501,8 +494,8 @@ namespace dgk {
 
 int nl_query(const dg_plan* p, int64_t out[3]) {
   out[0] = p->nl_exchange;
-  out[1] = chunk_nl(p, true)(1 << 30);
-  out[2] = chunk_nl(p, false)(1 << 30);
+  out[1] = nl_msteps(p, true);
+  out[2] = nl_msteps(p, false);
   return DG_OK;
 }
 

@@ -21,10 +21,12 @@
 
 #include "dg_advec.h"
 #include "dg_chain.h"
+#include "dg_shape.h"
 
 namespace dgk {
 
 constexpr int kBlock = 256;       // lanes per workgroup = elements per tile (incl. halo)
+static_assert(kBlock == kTileLanes, "the shape rules (dg_shape.h) count tiles of kBlock lanes");
 constexpr int kMaxNP = 9;         // N <= 8
 constexpr int kArgmaxParts = 1024;
 
@@ -458,13 +460,14 @@ __device__ __forceinline__ void stage_out(double* __restrict__ lds, const double
 // ---------------------------------------------------------------------------
 // Plan
 // ---------------------------------------------------------------------------
-struct dg_plan {
-  int N = 0, NP = 0;
-  int64_t K = 0, batch = 0, ktot = 0;
+// The tuning fields (dg_plan_tune) and the facts the shape rules read -- NP, nstages, uniform,
+// ktot -- are the base, dgk::Shape (dg_shape.h).
+struct dg_plan : dgk::Shape {
+  int N = 0;
+  int64_t K = 0, batch = 0;
   int64_t K_cap = 0;  // elements per trajectory the device buffers hold (dg_plan_reserve)
   double a = 0.0;
-  int inflow = 0, scheme = 0, nstages = 5;
-  bool uniform = true;
+  int inflow = 0, scheme = 0;
   double s_uniform = 0.0;  // 2/h for uniform meshes
   double r[dgk::kMaxNP], V[dgk::kMaxNP * dgk::kMaxNP], invV[dgk::kMaxNP * dgk::kMaxNP],
       Dr[dgk::kMaxNP * dgk::kMaxNP],
@@ -478,33 +481,8 @@ struct dg_plan {
   // dg_plan_mark / dg_plan_refine_marked (dg_mark.hip): the select's state words and digit
   // histograms (dgk::kMarkBytes, fixed size; the per-workgroup sums live in d_scratch2)
   void* d_mark = nullptr;
-  // tuning (dg_plan_tune): tile width of the step kernels (tile = 256*tile_width elements)
-  int tile_width = 1;  // dg_plan_create: 2 for N <= 2 (measured per-N)
-  int msteps = 4;  // time steps fused per launch (1, 2 or 4)
-  // the jump-record sweeps' shape (dg_lserk4_fwd_rec / _adj_rec: no snapshot per step, so
-  // long launches on wide tiles pay): tile width 1, 2 or 4, steps per launch 1..8
-  // defaults measured at N = 4, K = 2^20: 1024-element pair tiles, 10 steps per
-  // launch (a 20-step sweep is 10 + 10 launches)
-  int rec_tile_width = 2;
-  int rec_tile_width_fwd = 0;  // the forward record sweep's own tile width (0: as rec_tile_width)
-  int rec_msteps = 10;
-  // the forward's own record steps per launch: -1 by size (20 on 1024-element pair tiles up to
-  // 3*2^20 elements, else as rec_msteps), 0 as rec_msteps, > 0 explicit
-  int rec_msteps_fwd = -1;
-  int rec_lane_elems = 2;  // 2: the pair tiles of dg_rec.hip, 1: dg_advec.hip k_step/k_adj
-  // the p-enriched estimate's shape (dg_lserk4_adj_p, dg_dwr.hip): tile width 1 or 2 (256 or
-  // 512 elements), steps per launch 1, 2, 4 or 8 (8 on 512-element tiles)
-  int p_tile_width = 2;
-  int p_msteps = 4;
-  // 1: the estimate runs as ONE dataflow launch (k_adjp_flow) when its steps split into >= 2
-  // blocks of p_msteps; 0: one launch per block (dg_plan_create sets 1)
-  int p_flow = 0;
-  // 1: dg_lserk4_sweep_p runs forward and estimate as ONE dataflow launch (k_psweep) where the
-  // shape allows; 0: the chains (dg_plan_create sets 1)
-  int p_sweep = 0;
-  // the dataflow sweep (dg_lserk4_sweep_rec, dg_sweep.hip): its scratch (sync words, block
-  // states, indicator partials; grown on demand) and the switch (1: one dataflow launch where
-  // the shape allows it, 0: the launch-per-block pair)
+  // the dataflow sweep's scratch (sync words, block states, indicator partials; grown on
+  // demand)
   void* d_sweep = nullptr;
   int32_t* d_nl_list = nullptr;  // config-3 adjoint's troubled-tile list + per-step counts
   int64_t nl_list_tiles = 0, nl_list_steps = 0;
@@ -518,37 +496,13 @@ struct dg_plan {
   // scratch regions a grown scratch replaced: kept until the plan is destroyed, because a HIP
   // graph captured earlier still holds their addresses in its kernel arguments
   std::vector<void*> sweep_retired;
-  // watchdog: polls before a waiting work item gives up (0: the default, ~2^20; tests set 1)
-  int sweep_spin_limit = 0;
   // the watchdog's host-visible flag (mapped page-locked word; the device alias is what the
   // kernel writes): set by a work item that gave up, read without a sync by the next sweep
   // call (which then fails) and cleared by dg_sweep_status
   uint32_t* h_sweep_err = nullptr;
   uint32_t* d_sweep_err = nullptr;
-  int rec_sweep = 1;
-  // the dataflow sweep's workgroup waves (tiles of 128 * waves elements): 0 = as the record
-  // sweeps' tile width (4 * rec_tile_width), else 4, 8, 12 or 16 (12 / 16: dataflow only, both
-  // directions on that tile, whatever the launch chains' widths; 16 at Np <= 5)
-  int sweep_waves = 0;
-  // consecutive elements per lane of the dataflow sweep's tiles: 2 (pair tiles), or 4 at
-  // Np <= 3 on 4- or 8-wave workgroups (tiles of 64 * 4 * waves elements)
-  int sweep_lane_elems = 2;
-  // how the dataflow sweep's tiles exchange faces: 0 through LDS with a workgroup barrier per
-  // Horner level (dg_rec_tiles.h), 1 overlapped waves: DPP within a wave, one LDS exchange and
-  // barrier per step (dg_ovl_tiles.h)
-  int sweep_exchange = 0;
-  // how the config-3 kernels (nonlinear flux / per-stage limiter, dg_burgers*.hip) exchange
-  // neighbour values: 0 workgroup tiles through LDS, a barrier per exchange (dg_burgers.hip);
-  // 1 overlapped waves, DPP shifts, no barrier inside a step (dg_burgers_ov.hip)
-  int nl_exchange = 0;
-  // dg_lserk4_fwd with snapshots: 0 the stage-loop kernels (k_step / wave tiles; bit-identical
-  // to the record sweeps' stage-loop kernels), 1 Horner-form pair tiles (k_step_rps, dg_rec.hip;
-  // tiles of 512 * tile_width elements, msteps steps per launch)
-  int snap_pairs = 0;
   uint64_t* sweep_trace = nullptr;  // dg_plan_sweep_trace: per-item timestamps (profiling)
   int cu_count = 0;  // compute units of the plan's device (the dataflow grid)
-  int xcd_order = 1;  // XCD-aware tile order
-  int lane_elems = 0;  // 0: workgroup tiles (one element per lane); 2 or 4: wave tiles
   // physics (dg_plan_set_physics): DG_FLUX_LINEAR / DG_FLUX_BURGERS, SlopeLimitN per stage
   int flux = 0;
   int limiter = 0;
@@ -557,11 +511,6 @@ struct dg_plan {
 };
 
 namespace dgk {
-
-// Tile width of the forward record sweep (the adjoint's is rec_tile_width).
-inline int rec_fwd_width(const dg_plan* p) {
-  return p->rec_tile_width_fwd ? p->rec_tile_width_fwd : p->rec_tile_width;
-}
 
 inline double inflow_value(const dg_plan* p, double t) {
   if (p->inflow == DG_INFLOW_ZERO) return 0.0;
@@ -648,8 +597,6 @@ template <int NP> bool make_eo(const dg_plan* p, double scale, EOArgs<NP>* out, 
   return ok;
 }
 
-inline unsigned grid_for(int64_t n, int64_t per) { return unsigned((n + per - 1) / per); }
-
 // Dispatch on Np = 2 .. MAXNP: f(std::integral_constant<int, NP>) -> int.  Only the orders of
 // the range are instantiated (pair tiles and the general kernels 9, wave tiles and the
 // p-estimate 8).
@@ -689,13 +636,6 @@ inline auto field_copy(int64_t field, hipStream_t st) {
   };
 }
 
-// The launch shape of the linear forward sweep: steps per launch (before the caps of the tile
-// shape), elements per lane of the wave tiles (0: stage-loop workgroup tiles), pair-tile
-// snapshots.  The plan's own (msteps, lane_elems, snap_pairs) for dg_lserk4_fwd;
-// dg_lserk4_sweep_p marches at {4, 0, 0}.
-struct FwdShape {
-  int msteps, lane_elems, snap_pairs;
-};
 // The snapshot march of the linear forward (dg_advec.hip): snapshots[0] = u, rows 1 .. nsteps,
 // u = u^nsteps; tn: the nsteps + 1 time levels.
 int fwd_march(const dg_plan* p, FwdShape s, double* u, const double* tn, double dt, int nsteps,
@@ -725,16 +665,10 @@ struct SweepBufs {
   uint32_t* err_host;  // nullable: the plan's host-visible watchdog flag (d_sweep_err)
   int32_t spin_limit;  // 0: the default
 };
-int sweep_tile_elems(const dg_plan* p, int waves);
 int sweep_waves_per_simd(const dg_plan* p, int waves);  // the kernel's occupancy target (0: none)
-// work items / last-block adjoint tiles of a dataflow sweep over the plan's ktot elements, or
-// over `elems` (>= 0: the scratch sizing for the reserved capacity)
-int64_t sweep_items(const dg_plan* p, int waves, int msf, int msa, int nsteps, int64_t elems = -1);
-int64_t sweep_tiles_adj(const dg_plan* p, int waves, int msa, int64_t elems = -1);
 int sweep_launch_rec(dg_plan* p, int waves, int msf, int msa, const SweepBufs& b, double t0,
                      double dt, int nsteps, int mode, hipStream_t st);
 int sweep_sync_words();
-int sweep_max_steps();
 // The plan's dataflow scratch (dg_advec.hip): a control region of `sync_bytes` (zeroed where
 // newly covered) followed by `data_bytes`; *data = the data region.
 int sweep_scratch(dg_plan* p, size_t sync_bytes, size_t data_bytes, hipStream_t st, char** data);

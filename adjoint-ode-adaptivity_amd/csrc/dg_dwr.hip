@@ -753,7 +753,6 @@ int launch_adjp_flow(dg_plan* lo, const dg_plan* hi, const PrEO<NPL>& pr, const 
 // forward's arithmetic is k_step's at MS steps per launch: bit-identical to dg_lserk4_fwd
 // with that steps-per-launch followed by dg_lserk4_adj_p.
 // ---------------------------------------------------------------------------
-constexpr int kPSMaxSteps = 32;  // 8 blocks of 4: the blocks' constants fit the kernarg segment
 
 template <int NPL, int MS> struct PSweepArgs {
   static constexpr int kMaxBlocks = kPSMaxSteps / MS;
@@ -1038,14 +1037,6 @@ int launch_adj_p_t(const dg_plan* lo, const dg_plan* hi, const PrEO<NPL>& pr, in
   return fail(DG_ERR_ARG, "p-estimate: unsupported steps per launch for this tile width");
 }
 
-// The estimate's steps per launch: the plan's setting (8 needs 512-element tiles), halved
-// until it fits the steps left.
-inline int p_msteps(const dg_plan* p) {
-  int m = p->p_msteps;
-  if (m == 8 && p->p_tile_width != 2) m = 4;
-  return m;
-}
-
 // f(integral_constant NPL, PrEO<NPL>) -> int with the even/odd blocks of the prolongation P
 // for the lo plan's order (Np <= 8).
 template <class F> int with_prolong(const dg_plan* lo, const double* P, F&& f) {
@@ -1074,15 +1065,9 @@ int check_pair(const dg_plan* lo, const dg_plan* hi) {
   return DG_OK;
 }
 
-// The dataflow form applies: the plan asks for it, the Horner kernels are selected, and the
-// steps split into 2 .. 40/MS blocks of the plan's steps per launch (4 on 256-element tiles;
-// 4 or 8 on 512-element tiles).
-bool p_flow_shape(const dg_plan* lo, int nsteps) {
-  const int m = p_msteps(lo);
-  const int h = p_horner();
-  return lo->p_flow && (h == 1 || h == 3) && (m == 4 || (m == 8 && lo->p_tile_width == 2)) &&
-         nsteps > 0 && nsteps % m == 0 && nsteps / m >= 2 && nsteps <= dgr::kSweepMaxSteps;
-}
+// The dataflow shapes of dg_shape.h under the process's DG_P_HORNER mode.
+bool p_flow_on(const dg_plan* lo, int nsteps) { return p_flow_shape(lo, nsteps, p_horner()); }
+bool p_sweep_on(const dg_plan* lo, int nsteps) { return p_sweep_shape(lo, nsteps, p_horner()); }
 
 // One dataflow launch of the whole estimate (k_adjp_flow).  Scratch: the lo plan's dataflow
 // region (sweep_scratch: control words, then the blocks' w outputs W[1..nb-1] and partial
@@ -1100,12 +1085,11 @@ int adjp_flow(dg_plan* lo, const dg_plan* hi, const double* P, double* w,
               int mode, bool term, int64_t* idx, double* value, int64_t* nonfinite,
               hipStream_t st) {
   const int m = p_msteps(lo), nb = nsteps / m, W = lo->p_tile_width;
-  const int64_t TE = int64_t(kBlock) * W - 10 * m;
-  const int64_t nT = (lo->ktot + TE - 1) / TE;
-  const int64_t nT_cap = (lo->K_cap * lo->batch + TE - 1) / TE;
+  const int64_t kcap = lo->K_cap * lo->batch;
+  const int64_t nT = p_tiles(lo, m, lo->ktot), nT_cap = p_tiles(lo, m, kcap);
   PFlowBufs b;
-  if (const int rc = p_flow_bufs(lo, hi, 0x5a, m, W, nsteps, int64_t(nb) * nT, int64_t(nb) * nT_cap,
-                                 nT, nT_cap, nb, w, eta != nullptr, idx, value, nonfinite, st, &b))
+  if (const int rc = p_flow_bufs(lo, hi, 0x5a, m, W, nsteps, p_flow_items(lo, nsteps, lo->ktot),
+                                 p_flow_items(lo, nsteps, kcap), nT, nT_cap, nb, w, eta != nullptr, idx, value, nonfinite, st, &b))
     return rc;
   return with_prolong(lo, P, [&](auto np, const auto& pr) -> int {
     if (W == 2 && m == 8)
@@ -1117,14 +1101,6 @@ int adjp_flow(dg_plan* lo, const dg_plan* hi, const double* P, double* w,
     return launch_adjp_flow<np, 1, 4>(lo, hi, pr, b, snapshots, eta, mode, tn, dt, nsteps, term,
                                       st);
   });
-}
-
-// The whole sweep as one dataflow launch applies: the estimate's dataflow shape at 4-step
-// blocks, the forward's stage-loop workgroup tiles (not the wave tiles of N <= 2), and
-// 2..8 blocks.
-bool p_sweep_shape(const dg_plan* lo, int nsteps) {
-  return lo->p_sweep && p_flow_shape(lo, nsteps) && p_msteps(lo) == 4 && lo->lane_elems == 0 &&
-         lo->nstages == 5 && nsteps <= kPSMaxSteps;
 }
 
 // Scratch and control words of a dataflow launch over `items` work items whose last block has
@@ -1174,12 +1150,11 @@ int psweep(dg_plan* lo, const dg_plan* hi, const double* P, double* snapshots, d
            const double* tn, double dt, int nsteps, double* eta, int mode, int64_t* idx,
            double* value, int64_t* nonfinite, hipStream_t st) {
   const int m = 4, nb = nsteps / m, W = lo->p_tile_width;
-  const int64_t TE = int64_t(kBlock) * W - 10 * m;
-  const int64_t nT = (lo->ktot + TE - 1) / TE;
-  const int64_t nT_cap = (lo->K_cap * lo->batch + TE - 1) / TE;
+  const int64_t kcap = lo->K_cap * lo->batch;
+  const int64_t nT = p_tiles(lo, m, lo->ktot), nT_cap = p_tiles(lo, m, kcap);
   PFlowBufs b;
-  if (const int rc = p_flow_bufs(lo, hi, 0x5b, m, W, nsteps, 2 * int64_t(nb) * nT,
-                                 2 * int64_t(nb) * nT_cap, nT, nT_cap, nb, w, eta != nullptr, idx,
+  if (const int rc = p_flow_bufs(lo, hi, 0x5b, m, W, nsteps, p_sweep_items(lo, nsteps, lo->ktot),
+                                 p_sweep_items(lo, nsteps, kcap), nT, nT_cap, nb, w, eta != nullptr, idx,
                                  value, nonfinite, st, &b))
     return rc;
   return with_prolong(lo, P, [&](auto np, const auto& pr) -> int {
@@ -1219,7 +1194,7 @@ int adj_p_impl(dg_plan* lo, dg_plan* hi, const double* P, double* w, const doubl
   }
   const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
   const bool assign = flags & DG_ADJ_ETA_ASSIGN, abs = flags & DG_ADJ_ETA_ABS;
-  if (p_flow_shape(lo, nsteps))
+  if (p_flow_on(lo, nsteps))
     return adjp_flow(lo, hi, P, w, snapshots, tn.data(), dt, nsteps, eta,
                      chain::eta_sweep_mode(eta != nullptr, assign, abs), term, idx, value,
                      nonfinite, st);
@@ -1280,31 +1255,21 @@ int dg_lserk4_adj_p_refine(dg_plan* lo, dg_plan* hi, const double* P, double* w,
 
 int dg_plan_query_p_flow(const dg_plan* lo, int nsteps, int* out) {
   if (!lo || !out) return fail(DG_ERR_ARG, "null argument");
-  *out = p_flow_shape(lo, nsteps) ? 1 : 0;
+  *out = p_flow_on(lo, nsteps) ? 1 : 0;
   return DG_OK;
 }
 
 int dg_plan_query_p_sweep(const dg_plan* lo, int nsteps, int* out) {
   if (!lo || !out) return fail(DG_ERR_ARG, "null argument");
-  *out = p_sweep_shape(lo, nsteps) ? 1 : 0;
+  *out = p_sweep_on(lo, nsteps) ? 1 : 0;
   return DG_OK;
 }
 
 int dg_plan_query_p_trace(const dg_plan* lo, int nsteps, int64_t out[3]) {
   if (!lo || !out) return fail(DG_ERR_ARG, "null argument");
-  // work items of each launch (k_adjp_flow: blocks x tiles; k_psweep: twice, forward and
-  // estimate blocks), as adjp_flow / psweep size them
-  const int W = lo->p_tile_width;
-  out[0] = out[1] = 0;
-  if (p_flow_shape(lo, nsteps)) {
-    const int m = p_msteps(lo);
-    const int64_t TE = int64_t(kBlock) * W - 10 * m;
-    out[0] = int64_t(nsteps / m) * ((lo->ktot + TE - 1) / TE);
-  }
-  if (p_sweep_shape(lo, nsteps)) {
-    const int64_t TE = int64_t(kBlock) * W - 10 * 4;
-    out[1] = 2 * int64_t(nsteps / 4) * ((lo->ktot + TE - 1) / TE);
-  }
+  // work items of each launch, as adjp_flow / psweep size them
+  out[0] = p_flow_on(lo, nsteps) ? p_flow_items(lo, nsteps, lo->ktot) : 0;
+  out[1] = p_sweep_on(lo, nsteps) ? p_sweep_items(lo, nsteps, lo->ktot) : 0;
   out[2] = 8;  // trace words per item
   return DG_OK;
 }
@@ -1329,7 +1294,7 @@ int dg_lserk4_sweep_p(dg_plan* lo, dg_plan* hi, const double* P, double* snapsho
     return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const std::vector<double> tn = chain::time_levels(t0, dt, nsteps);
-  if (!p_sweep_shape(lo, nsteps)) {
+  if (!p_sweep_on(lo, nsteps)) {
     // the launch chains: the snapshot forward in place from snapshot 0 -- on the stage-loop
     // workgroup tiles at 4 steps per launch, the dataflow launch's forward blocks, so that the
     // result does not depend on whether nsteps fits that launch -- then the estimate

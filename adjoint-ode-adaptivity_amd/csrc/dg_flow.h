@@ -8,8 +8,7 @@
 
 namespace dgr {
 
-constexpr int kSweepMaxSteps = 40;   // steps per dataflow launch (block constants are kernargs)
-constexpr int kSweepMaxBlocks = 8;   // jump sweep: blocks per direction (kSweepMaxSteps / 5)
+constexpr int kSweepMaxBlocks = 8;   // jump sweep: blocks per direction (kSweepMaxSteps / 5, dg_shape.h)
 // control words (uint32 index): a 64-bit take counter, the error word, a 64-bit arrival
 // counter of the fused refine decision, then one flag per item
 constexpr int kSyncHead = 0, kSyncErr = 2, kSyncArrive = 4, kSyncFlags = 16;

@@ -31,9 +31,8 @@
 
 namespace dgr {
 
-constexpr int kOvG = 6;               // ghost elements per window end: >= 5 (a step's cone), even
+// kOvG ghost elements per window end, kOvS elements a wave owns: dg_shape.h
 constexpr int kOvGL = kOvG / 2;       // ghost lanes per window end
-constexpr int kOvS = 128 - 2 * kOvG;  // elements a wave owns
 
 template <int NP, int NW> struct OvGeo {
   static constexpr int LB = 64 * NW;

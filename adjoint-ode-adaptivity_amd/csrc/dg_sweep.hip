@@ -53,10 +53,6 @@ int sweep_launch_ov(dg_plan* p, int waves, int msf, int msa, const SweepBufs& b,
                     double dt, int nsteps, int mode, hipStream_t st);
 
 
-int sweep_tile_elems(const dg_plan* p, int waves) {
-  return p->sweep_exchange == 1 ? waves * kOvS + 2 * kOvG : 64 * p->sweep_lane_elems * waves;
-}
-
 int sweep_waves_per_simd(const dg_plan* p, int waves) {
   const int E = p->sweep_lane_elems, X = p->sweep_exchange;
   if (E != 2) return 0;
@@ -90,19 +86,6 @@ int sweep_waves_per_simd(const dg_plan* p, int waves) {
   return w == 1 ? 0 : w;
 }
 
-int64_t sweep_items(const dg_plan* p, int waves, int msf, int msa, int nsteps, int64_t elems) {
-  const int64_t n = elems >= 0 ? elems : p->ktot;
-  const int T = sweep_tile_elems(p, waves);
-  const int64_t nTF = grid_for(n, T - 2 * ((msf * 5 + 2) & ~1));
-  const int64_t nTA = grid_for(n, T - 2 * ((msa * 5 + 1) & ~1));
-  return int64_t(nsteps / msf) * nTF + int64_t(nsteps / msa) * nTA;
-}
-
-int64_t sweep_tiles_adj(const dg_plan* p, int waves, int msa, int64_t elems) {
-  const int64_t n = elems >= 0 ? elems : p->ktot;
-  return grid_for(n, sweep_tile_elems(p, waves) - 2 * ((msa * 5 + 1) & ~1));
-}
-
 int sweep_launch_rec(dg_plan* p, int waves, int msf, int msa, const SweepBufs& b, double t0,
                      double dt, int nsteps, int mode, hipStream_t st) {
   if (p->sweep_exchange == 1) return sweep_launch_ov(p, waves, msf, msa, b, t0, dt, nsteps, mode, st);
@@ -111,7 +94,6 @@ int sweep_launch_rec(dg_plan* p, int waves, int msf, int msa, const SweepBufs& b
 }
 
 int sweep_sync_words() { return kSyncFlags; }
-int sweep_max_steps() { return kSweepMaxSteps; }
 int sweep_err_word() { return kSyncErr; }
 
 }  // namespace dgk

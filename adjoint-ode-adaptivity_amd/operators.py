@@ -212,21 +212,13 @@ class DGAdvection1D:
                      (_lib.DG_TUNE_SWEEP_TAKE, sweep_take),
                      (_lib.DG_TUNE_SWEEP_EXCHANGE, sweep_exchange),
                      (_lib.DG_TUNE_SNAP_PAIRS, snap_pairs),
-                     (_lib.DG_TUNE_NL_EXCHANGE, nl_exchange)):
+                     (_lib.DG_TUNE_NL_EXCHANGE, nl_exchange),
+                     (_lib.DG_TUNE_XCD_ORDER, xcd_order),
+                     (_lib.DG_TUNE_LANE_ELEMENTS, lane_elements),  # 0 = workgroup tiles
+                     (_lib.DG_TUNE_TILE_WIDTH, tile_width),
+                     (_lib.DG_TUNE_STEPS_PER_LAUNCH, steps_per_launch)):
       if val is not None:
         _lib.check(self._lib.dg_plan_tune(self._plan, key, int(val)), "dg_plan_tune")
-    if xcd_order is not None:
-      _lib.check(self._lib.dg_plan_tune(self._plan, _lib.DG_TUNE_XCD_ORDER, int(xcd_order)),
-                 "dg_plan_tune")
-    if lane_elements is not None:  # forward steps on one-wave tiles (0 = workgroup tiles)
-      _lib.check(self._lib.dg_plan_tune(self._plan, _lib.DG_TUNE_LANE_ELEMENTS,
-                                        int(lane_elements)), "dg_plan_tune")
-    if tile_width is not None:
-      _lib.check(self._lib.dg_plan_tune(self._plan, _lib.DG_TUNE_TILE_WIDTH,
-                                        int(tile_width)), "dg_plan_tune")
-    if steps_per_launch is not None:
-      _lib.check(self._lib.dg_plan_tune(self._plan, _lib.DG_TUNE_STEPS_PER_LAUNCH,
-                                        int(steps_per_launch)), "dg_plan_tune")
     self._query()
     return self
 
@@ -704,15 +696,11 @@ class DWREstimate:
     into 2 or more blocks of 4 (or 8 on 512-element tiles) steps (bit-identical); ``sweep``
     (0 / 1): ``sweep`` as the chains or as one dataflow launch (bit-identical)."""
     lib, plan = self.lo._lib, self.lo._plan
-    if sweep is not None:
-      _lib.check(lib.dg_plan_tune(plan, _lib.DG_TUNE_P_SWEEP, int(sweep)), "dg_plan_tune")
-    if flow is not None:
-      _lib.check(lib.dg_plan_tune(plan, _lib.DG_TUNE_P_FLOW, int(flow)), "dg_plan_tune")
-    if tile_width is not None:
-      _lib.check(lib.dg_plan_tune(plan, _lib.DG_TUNE_P_TILE_WIDTH, int(tile_width)), "dg_plan_tune")
-    if steps_per_launch is not None:
-      _lib.check(lib.dg_plan_tune(plan, _lib.DG_TUNE_P_STEPS_PER_LAUNCH, int(steps_per_launch)),
-                 "dg_plan_tune")
+    for key, val in ((_lib.DG_TUNE_P_SWEEP, sweep), (_lib.DG_TUNE_P_FLOW, flow),
+                     (_lib.DG_TUNE_P_TILE_WIDTH, tile_width),
+                     (_lib.DG_TUNE_P_STEPS_PER_LAUNCH, steps_per_launch)):
+      if val is not None:
+        _lib.check(lib.dg_plan_tune(plan, key, int(val)), "dg_plan_tune")
     q = (ctypes.c_int64 * 2)()
     _lib.check(lib.dg_plan_query_p(plan, q), "dg_plan_query_p")
     self.tile_width, self.steps_per_launch = int(q[0]), int(q[1])

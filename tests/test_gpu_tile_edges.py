@@ -822,7 +822,7 @@ def block_edge_case(pkg, gpu, N, ktot, point):
 @pytest.mark.parametrize("N", [1, 4])
 def test_halo_free_kernels(pkg, gpu, N, ktot):
   """rhs, prolong and init_sine, one element per lane on grids of grid_for(ktot, 256)
-  (csrc/dg_advec.hip:1558, :2048, csrc/dg_dwr.hip:1259), at 255 .. 257 and 511 .. 513; and
+  (csrc/dg_advec.hip:1261, :1754, csrc/dg_dwr.hip:1234), at 255 .. 257 and 511 .. 513; and
   slope_limit / slope_limit_1, whose k_limit tiles have H = 1 and own TE = 254 elements
   (csrc/dg_advec.hip:407-408, grids :1928, :1942), at their own TE-1 .. TE+2 and 2TE-1 .. 2TE+1
   as well (253 .. 256, 507 .. 509)."""

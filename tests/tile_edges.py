@@ -34,7 +34,7 @@ def geometry_fail(what):
 
 
 def grid_for(n, per):
-  return (n + per - 1) // per  # csrc/dg_common.h:651
+  return (n + per - 1) // per  # grid_for, csrc/dg_shape.h
 
 
 # --- owned extents (TE, H) per family, from the plan ----------------------------------
@@ -117,7 +117,8 @@ def check_sweep_items(op, nsteps, ext):
 
 def p_extents(op):
   """adjp / adjp_flow / psweep on tiles of 256*W lanes, one element per lane: H = 5*MS
-  (csrc/dg_dwr.hip:394, :484, :1103; the psweep's blocks are 4 steps, :1177)."""
+  (csrc/dg_dwr.hip:394, :484; the host side p_tiles, csrc/dg_shape.h; the psweep's blocks are 4
+  steps)."""
   W, MS = _q(op, "dg_plan_query_p", 2)
   return [(256 * W - 10 * MS, 5 * MS)]
 
@@ -160,7 +161,7 @@ def source_constant(name, file, pattern=None):
 
 def limiter_extents():
   """k_limit (slope_limit, slope_limit_1): tiles of kBlock lanes with H = 1, TE = kBlock - 2
-  (csrc/dg_advec.hip:407-408; launches grid_for(ktot, kBlock - 2), :1928, :1942)."""
+  (csrc/dg_advec.hip:407-408; launches grid_for(ktot, kBlock - 2), :1634, :1648)."""
   H = source_constant("k_limit H", "dg_advec.hip",
                       r"constexpr int H = (\d+);\s*constexpr int TE = kBlock - 2 \* H;")
   return [(source_constant("kBlock", "dg_common.h") - 2 * H, H)]
@@ -175,7 +176,7 @@ def nl_extents(op, snapshots, known):
   half tiles TH = TE/2, :290), or on overlapped waves (record or no limiter) G = kOwAdjG = 10:
   TE = 4 * 44 (csrc/dg_burgers_ov.hip:214, :363).  The constants are read from csrc/
   (``source_constant``): no query reports them.  With ``snapshots`` a third entry gives the
-  forward without snapshots where its steps per launch differ (csrc/dg_burgers.hip:493-496)."""
+  forward without snapshots where its steps per launch differ (nl_msteps, csrc/dg_shape.h)."""
   ex, ms_snap, ms_plain = _q(op, "dg_plan_query_nl", 3)
   kBlock = source_constant("kBlock", "dg_common.h")
   step_w = source_constant("kNLStepW", "dg_burgers.hip")
