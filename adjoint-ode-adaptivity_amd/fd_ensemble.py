@@ -60,18 +60,26 @@ class FDEnsemble:
     self._lib = _lib.load()
     self.history = []
 
+  def _grid(self):
+    """Step counts and device copies of dt, the cumulative coarse / fine times and np.interp's
+    case codes, uploaded once per grid (the upload waits for the stream; a sweep on an
+    unchanged grid only enqueues its launch)."""
+    key = self.times.tobytes()
+    if getattr(self, "_grid_cache", (None,))[0] != key:
+      dt_n = np.diff(self.times, 1)
+      dt_fine, nf = refine_all(dt_n, self.rf)
+      t_coarse = np.concatenate(([0], np.cumsum(dt_n)), axis=None)  # interpU (:27-28)
+      t_fine = np.concatenate(([0], np.cumsum(dt_fine)), axis=None)
+      t = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt,  # noqa: E731
+                                                      device=self.dev)
+      self._grid_cache = (key, (dt_n.size, nf, t(dt_n), t(t_coarse), t(t_fine),
+                                t(interp_codes(t_coarse, t_fine), torch.int32)))
+    return self._grid_cache[1]
+
   def sweep(self, with_v=False):
     """One forward + adjoint + indicator sweep on the current grid for every member.
     Returns U [n+1, n_ics], V [n*rf+1, n_ics] (or None), err_steps [n_ics, n]."""
-    dt_n = np.diff(self.times, 1)
-    n = dt_n.size
-    dt_fine, nf = refine_all(dt_n, self.rf)
-    t_coarse = np.concatenate(([0], np.cumsum(dt_n)), axis=None)  # interpU (:27-28)
-    t_fine = np.concatenate(([0], np.cumsum(dt_fine)), axis=None)
-    t = lambda x, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(x), dtype=dt,  # noqa: E731
-                                                    device=self.dev)
-    dtd, tcd, tfd = t(dt_n), t(t_coarse), t(t_fine)
-    codes = t(interp_codes(t_coarse, t_fine), torch.int32)
+    n, nf, dtd, tcd, tfd, codes = self._grid()
     U = torch.empty((n + 1, self.n_ics), dtype=torch.float64, device=self.dev)
     V = torch.empty((nf + 1, self.n_ics), dtype=torch.float64, device=self.dev) if with_v else None
     err = torch.empty((self.n_ics, n), dtype=torch.float64, device=self.dev)

@@ -646,10 +646,15 @@ class DGAdvection1D:
     return cand
 
   def init_sine(self, amp, freq, phase, out=None):
-    """u_b(x) = amp[b] sin(2 pi freq[b] x + phase[b]) on the device (ensemble ICs)."""
+    """u_b(x) = amp[b] sin(2 pi freq[b] x + phase[b]) on the device (ensemble ICs).
+    ``amp`` / ``freq`` / ``phase``: host sequences (uploaded here: that copy waits for the
+    stream) or contiguous CUDA float64 tensors on the plan's device (nothing waits)."""
     out = self.new_field() if out is None else out
-    vals = [torch.as_tensor(np.asarray(v, dtype=np.float64), device=self.device)
+    vals = [v if isinstance(v, torch.Tensor) and v.is_cuda
+            else torch.as_tensor(np.asarray(v, dtype=np.float64), device=self.device)
             for v in (amp, freq, phase)]
+    for v, name in zip(vals, ("amp", "freq", "phase")):
+      _cuda(v, torch.float64, name, 0, self.device)
     for v in vals:
       if v.numel() != self.batch:
         raise ValueError("amp/freq/phase need one value per trajectory")

@@ -11,15 +11,29 @@
  * Conventions
  *  - Layout: element-major fp64, u[e*Np + i] with e = b*K + k (trajectory b, element k),
  *    byte-identical to MATLAB's Np x K column-major array for one trajectory.
- *  - All array arguments of compute calls are DEVICE pointers owned by the caller.  The
- *    library never frees caller memory and never allocates inside compute calls; scratch
- *    lives in the plan.  Host pointers appear only in dg_plan_create (copied).
+ *  - All array arguments of compute calls are DEVICE pointers owned by the caller, unless a
+ *    comment says HOST (the operator arrays of dg_plan_create, P of the p-estimate, A of
+ *    dg_field_*_children, offsets of dg_resnet_*, dg_plan_get_mesh's VX, n_split, status:
+ *    small, read or written during the call itself).  The library never frees caller memory.
+ *    Scratch lives in the plan: dg_plan_create and dg_plan_reserve allocate it, and in the
+ *    steady state no compute call allocates.  The exceptions grow a plan region on first use
+ *    or when a call needs more than any earlier one, and say so in a "Sync:" line: the
+ *    dataflow region of dg_lserk4_sweep_rec / _refine / dg_lserk4_adj_p(_refine) /
+ *    dg_lserk4_sweep_p, and the tile list of dg_lserk4_adj(_ex) with a decision record.
  *  - Every function returns 0 (DG_OK) or a negative DG_ERR_* code; dg_last_error() gives
  *    the message of the last failure on the calling thread.  No exception crosses the ABI.
- *  - Compute calls are asynchronous on `stream` (a hipStream_t, NULL = default stream);
- *    the caller synchronises.  A plan may be shared by threads that use different streams
- *    for dg_advec_rhs / dg_slope_limit_n; dg_lserk4_fwd / dg_lserk4_adj / dg_argmax use
- *    plan scratch and must not run concurrently on one plan.
+ *  - Compute calls (the ones with a `stream` parameter) enqueue every launch, fill and copy
+ *    on `stream` (a hipStream_t, NULL = default stream) and return without waiting for it;
+ *    the caller synchronises.  An entry point that waits -- for the stream, for the device,
+ *    or only on first use or growth -- has a "Sync:" line in its comment that says for what
+ *    and when; one without such a line never waits (tests/test_gpu_stream_order.py holds
+ *    both directions on a delayed side stream).  Plan scratch: every compute call that takes
+ *    a non-const dg_plan* uses it, except dg_slope_limit_n / dg_slope_limit_1, so no two of
+ *    those calls may run concurrently on one plan (dg_lserk4_adj_p(_refine) and
+ *    dg_lserk4_sweep_p use both plans').  The calls that take a const dg_plan* or none
+ *    (dg_advec_rhs, dg_init_sine, dg_prolong, dg_field_to_children / _from_children, the
+ *    plan-free kernels) and the two limiters use no plan scratch: threads on different
+ *    streams may share a plan for them.
  *  - Aliasing and alignment: the byte ranges of any two array arguments of one compute call
  *    must be disjoint, unless that entry point's comment has an "Alias:" line that says
  *    otherwise.  A range is [pointer, pointer + bytes) with the bytes the call reads or writes
@@ -84,7 +98,10 @@ int dg_plan_create(int N, int64_t K, int64_t batch,
                    const double* Dr, const double* LIFT, const double* VX,
                    double a, int inflow_variant, int time_scheme, dg_plan** out);
 
-/* Destroy a plan (frees its device scratch).  NULL is a no-op. */
+/* Destroy a plan (frees its device scratch).  NULL is a no-op.
+ * Sync: the device (hipFree waits for it; a plan that ran a dataflow launch synchronises the
+ * device first): work of the plan still enqueued on any stream finishes before its scratch
+ * goes. */
 int dg_plan_destroy(dg_plan* plan);
 
 /* Query plan sizes: out[0]=N, out[1]=Np, out[2]=K, out[3]=batch, out[4]=uniform mesh (0/1),
@@ -228,7 +245,10 @@ int dg_plan_set_physics(dg_plan* plan, int flux, int limiter);
  * device); never shrinks; a no-op when the capacity suffices.  The dataflow sweep's scratch is
  * sized for the reserved capacity, so refines within it reuse it; a growing reserve frees the
  * plan's old scratch (also scratch regions earlier sweeps outgrew), so HIP graphs captured
- * before it must be re-captured. */
+ * before it must be re-captured.
+ * Sync: the device, on every call that grows the capacity (hipDeviceSynchronize, then
+ * hipMalloc, blocking copies of the mesh and hipFree); a call the capacity already covers
+ * returns at once. */
 int dg_plan_reserve(dg_plan* plan, int64_t K_capacity);
 
 /* Refine on the device: split element idx[0] (device int64 in [0, K), e.g. dg_argmax's
@@ -281,7 +301,9 @@ int dg_plan_mark(dg_plan* plan, const double* eta, int strategy, double param,
  * counted: marks inside its first K entries is refused before anything is enqueued, marks
  * inside the rest after the count (which has read marks and written plan scratch only),
  * before parent or the mesh is written.  n_split is a host pointer the call writes itself
- * after its synchronisation, so it has no device range and takes no part. */
+ * after its synchronisation, so it has no device range and takes no part.
+ * Sync: the stream, on every call (after the scan of the marks, before the mesh is touched);
+ * the split's own kernels are enqueued after it and not waited for. */
 int dg_plan_refine_marked(dg_plan* plan, const uint8_t* marks, int32_t* parent, int64_t* n_split,
                           void* stream);
 
@@ -321,7 +343,9 @@ int dg_field_to_children(const dg_plan* plan, const int32_t* parent, int64_t k_o
 int dg_field_from_children(const dg_plan* plan, const int32_t* parent, int64_t k_old,
                            const double* A, const double* in_new, double* out_old, void* stream);
 
-/* Copy the plan's current K+1 vertex coordinates to the host array VX (synchronous). */
+/* Copy the plan's current K+1 vertex coordinates to the host array VX (synchronous).
+ * Sync: the device, on every call (hipDeviceSynchronize before a blocking copy: refines
+ * enqueued on any stream are in the result). */
 int dg_plan_get_mesh(const dg_plan* plan, double* VX);
 
 /* rhs = AdvecRHS1D(u, t, a)   — utils/AdvecRHS1D.m:1-20 (inline copy One_code.mlx:124-134).
@@ -381,7 +405,12 @@ enum { DG_ADJ_ETA_ASSIGN = 1, DG_ADJ_ETA_ABS = 2 };
  * (the result equals dg_prolong into w first, bit for bit). */
 enum { DG_ADJ_P_TERMINAL_PROLONG = 8 };
 /* Alias: w == snapshots + nsteps*field exactly, as dg_lserk4_adj; eta and decisions overlap
- * nothing (decisions counts on plans with a per-stage limiter only). */
+ * nothing (decisions counts on plans with a per-stage limiter only).
+ * Sync: only on first use or growth, and only with decisions on a plan with a per-stage
+ * limiter -- the troubled-tile list (one entry per tile of the reserved capacity, one count
+ * per step, at least 64 steps) is allocated by the first such call and again by one with more
+ * tiles or steps: that call waits for the stream, frees the old list and allocates the new one
+ * (hipFree and hipMalloc may wait for the device).  Never in the steady state. */
 int dg_lserk4_adj_ex(dg_plan* plan, double* w, const double* snapshots, double t0, double dt,
                      int nsteps, double src_coef, double* eta, int flags,
                      const uint16_t* decisions, void* stream);
@@ -427,7 +456,12 @@ int dg_lserk4_adj_rec(dg_plan* plan, double* w, const double* jumps, double t0, 
  *   jumps: the record (layout of dg_lserk4_fwd_rec), written and read by the call.
  *   eta (nullable), flags: DG_ADJ_ETA_ASSIGN / DG_ADJ_ETA_ABS as dg_lserk4_adj_rec.
  * Scratch: the plan's (block states, indicator partials and the launch's sync words, grown on
- * the first call of a shape: make that call outside HIP-graph capture). */
+ * the first call of a shape: make that call outside HIP-graph capture).
+ * Sync: only on first use or growth -- the
+ * first call of a plan maps 64 bytes of page-locked host memory (the watchdog flag), and a
+ * call that needs a larger dataflow region than any before it allocates a new one with
+ * hipMalloc (the old region is retired, not freed); the runtime may wait for the device in
+ * either.  Never in the steady state. */
 enum { DG_SWEEP_TERMINAL_STATE = 4 };
 int dg_lserk4_sweep_rec(dg_plan* plan, const double* u0, double* uN, double* w, double* jumps,
                         double t0, double dt, int nsteps, double* eta, int flags, void* stream);
@@ -436,7 +470,9 @@ int dg_lserk4_sweep_rec(dg_plan* plan, const double* u0, double* uN, double* w, 
  * python/Main_finite_difference.py:336-341 (np.argmax of the indicator) up to the split.
  * In the dataflow launch the last adjoint block's tiles publish their winners and the last
  * one to arrive reduces them (no separate reduction kernels); otherwise dg_argmax_ex runs
- * after the two launch chains.  Same results either way.  eta is required; nsteps >= 1. */
+ * after the two launch chains.  Same results either way.  eta is required; nsteps >= 1.
+ * Sync: only on first use or growth, as dg_lserk4_sweep_rec (the refine decision's slots make
+ * the region a little larger than the plain sweep's). */
 int dg_lserk4_sweep_refine(dg_plan* plan, const double* u0, double* uN, double* w,
                            double* jumps, double t0, double dt, int nsteps, double* eta,
                            int flags, int64_t* idx, double* value, int64_t* nonfinite_count,
@@ -458,7 +494,9 @@ int dg_plan_query_sweep_kernel(const dg_plan* plan, int nsteps, int64_t out[8]);
  * (states, indicator rows, its refine candidate): eta and the fused refine value are then not
  * finite and nonfinite_count counts it.  The flag is also raised in mapped host memory: every
  * later dg_lserk4_sweep_rec / dg_lserk4_sweep_refine call of the plan returns DG_ERR_HIP
- * (without a device sync) until dg_sweep_status clears it. */
+ * (without a device sync) until dg_sweep_status clears it.
+ * Sync: the stream, on every call once the plan has its dataflow region (twice when the flag
+ * was raised: the clearing fill is waited for too); before that it returns at once. */
 int dg_sweep_status(dg_plan* plan, int* status, void* stream);
 /* Profiling: with trace non-null (device), every later dataflow launch of the plan records
  * per work item the wall-clock (100 MHz) times it was taken and its producers were done and
@@ -499,7 +537,11 @@ int dg_plan_sweep_trace(dg_plan* plan, uint64_t* trace);
  *   DG_ADJ_P_TERMINAL_PROLONG (w on entry := P u^nsteps, formed in the kernel).
  * Scratch: the hi plan's; the dataflow form (DG_TUNE_P_FLOW) the lo plan's dataflow region
  * (as dg_lserk4_sweep_rec; its watchdog flag is the lo plan's, dg_sweep_status).  Neither plan
- * may be used concurrently. */
+ * may be used concurrently.
+ * Sync (dg_lserk4_adj_p): only on first use or growth -- the dataflow form maps the lo plan's
+ * watchdog flag and grows its dataflow region as dg_lserk4_sweep_rec does (hipHostMalloc,
+ * hipMalloc).  Never in the steady state, and never as a launch chain.  dg_prolong never
+ * waits. */
 int dg_prolong(const dg_plan* lo, const dg_plan* hi, const double* P, const double* u,
                double* u_hi, void* stream);
 int dg_lserk4_adj_p(dg_plan* lo, dg_plan* hi, const double* P, double* w,
@@ -510,7 +552,8 @@ int dg_lserk4_adj_p(dg_plan* lo, dg_plan* hi, const double* P, double* w,
  * idx, value, nonfinite_count), as dg_lserk4_sweep_refine does for the jump indicator: fused
  * into the launch (the last block's tiles reduce their winners) when the estimate runs as one
  * dataflow launch (DG_TUNE_P_FLOW), else a separate reduction.  eta and idx are required.
- * Replaces python/Main_finite_difference.py:336-341 (np.argmax of the indicator). */
+ * Replaces python/Main_finite_difference.py:336-341 (np.argmax of the indicator).
+ * Sync: only on first use or growth, as dg_lserk4_adj_p. */
 int dg_lserk4_adj_p_refine(dg_plan* lo, dg_plan* hi, const double* P, double* w,
                            const double* snapshots, double t0, double dt, int nsteps,
                            double* eta, int flags, int64_t* idx, double* value,
@@ -531,7 +574,8 @@ int dg_plan_query_p_flow(const dg_plan* lo, int nsteps, int* out);
  * plan's steps per launch) + dg_lserk4_adj_p(_refine): the same bits either way, and the same
  * as dg_lserk4_fwd_ex with the lo plan's steps per launch at 4 followed by dg_lserk4_adj_p.  flags: DG_ADJ_ETA_ASSIGN /
  * _ABS.  Replaces the reference's forward march + adjoint march + error estimate
- * (matlab/MAIN.m:32-34, adj_march.m:103-117). */
+ * (matlab/MAIN.m:32-34, adj_march.m:103-117).
+ * Sync: only on first use or growth, as dg_lserk4_adj_p (the chains' estimate included). */
 int dg_lserk4_sweep_p(dg_plan* lo, dg_plan* hi, const double* P, double* snapshots, double* w,
                       double t0, double dt, int nsteps, double* eta, int flags, int64_t* idx,
                       double* value, int64_t* nonfinite_count, void* stream);

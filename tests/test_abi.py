@@ -154,3 +154,53 @@ def test_header_states_the_alias_rule_for_every_entry_point():
                "dg_stream_copy", "dg_plan_refine", "dg_field_to_children",
                "dg_field_from_children"):
     assert name in default, name
+
+
+# Entry points that are not purely asynchronous: each says in a "Sync:" (or, in a shared comment,
+# "Sync (name):") line what it waits for -- "the stream" or "the device" on every call, or "only
+# on first use or growth" together with what it allocates.  tests/test_gpu_stream_order.py
+# imports this: on a delayed side stream a warmed-up call must come back while the delay is
+# still running, unless it is listed here as waiting for the stream or the device on every
+# call -- and those must not.
+SYNC_LINES = {"dg_plan_destroy": "device", "dg_plan_reserve": "device",
+              "dg_plan_get_mesh": "device", "dg_plan_refine_marked": "stream",
+              "dg_sweep_status": "stream", "dg_lserk4_adj_ex": "first use",
+              "dg_lserk4_sweep_rec": "first use", "dg_lserk4_sweep_refine": "first use",
+              "dg_lserk4_adj_p": "first use", "dg_lserk4_adj_p_refine": "first use",
+              "dg_lserk4_sweep_p": "first use"}
+SYNC_KINDS = {"the stream": "stream", "the device": "device",
+              "only on first use or growth": "first use"}
+
+
+def test_header_says_which_entry_points_wait():
+  """The Conventions block promises that compute calls enqueue on `stream` and return without
+  waiting, that an entry point that waits says so in a "Sync:" line, and that nothing allocates
+  in the steady state; the entry points with such a line, and what each waits for, are exactly
+  the ones listed above.  Every one that waits only on first use or growth names what it
+  allocates."""
+  src = open(HEADER).read()
+  head = " ".join(src[:src.index("#ifndef DG_ADVEC_H")].replace("*", " ").split())
+  for phrase in ("enqueue every launch, fill and copy on `stream`", "return without waiting",
+                 'has a "Sync:" line in its comment', "one without such a line never waits",
+                 "in the steady state no compute call allocates",
+                 "every compute call that takes a non-const dg_plan uses it, except "
+                 "dg_slope_limit_n / dg_slope_limit_1"):
+    assert phrase in head, phrase
+  assert "never allocates inside compute calls" not in head
+  fns = entry_point_comments()
+  found = {}
+  for name, (params, comment) in fns.items():
+    flat = " ".join(comment.replace("*", " ").split())
+    for m in re.finditer(r"Sync(?: \((\w+)\))?: (.*?)(?=$| Alias| Sync)", flat):
+      if m.group(1) not in (None, name):
+        continue
+      kinds = [k for text, k in SYNC_KINDS.items() if m.group(2).startswith(text)]
+      assert len(kinds) == 1, (name, m.group(2)[:60])
+      found[name] = kinds[0]
+      if kinds[0] == "first use":
+        assert re.search(r"hipMalloc|hipHostMalloc|as dg_lserk4_\w+", m.group(2)), name
+  assert found == SYNC_LINES, (sorted(set(found.items()) ^ set(SYNC_LINES.items())))
+  # a waiting entry point without a stream parameter waits for the device
+  for name, kind in SYNC_LINES.items():
+    has_stream = bool(re.search(r"void\s*\*\s*stream", fns[name][0]))
+    assert has_stream or kind == "device", name
